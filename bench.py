@@ -10,10 +10,23 @@ block-rows over N ranks (strong scaling), launched by the driver as
 torchrun with one rank per GPU over RCCL.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--features k]
+                  [--dump-outputs DIR] [--full]
 
 Timing: W untimed warmup steps, then exactly K steps bracketed by
 barrier + torch.cuda.synchronize on both sides; MAX over ranks; rank 0
-prints ONE JSON line. Inputs are resident in HBM before the timed region.
+prints ONE JSON line. Inputs are resident in HBM before the timed region
+and seeded, so the same arguments give the same inputs on every run.
+On a single GPU the timed loop replays a captured two-step hipGraph; an odd
+K ends on one uncaptured step, so `ms_per_step` then averages K-1 replayed
+steps and one plainly launched one (the launch cost is microseconds against
+~50 ms of kernel time).
+
+A plain run does only that: set up, warm up, time the K steps, write the
+last step's result stripe if `--dump-outputs DIR` is given, print the line
+(`roofline` and `cpu_baseline` are null). `--full` adds the secondary
+measurements described below, each in a pass of its own outside the timed
+region: the streaming HBM peak, the HIP-event roofline pass, the rocprofv3
+traffic probe and the CPU baseline.
 
 The `roofline` object reports the dominant kernel (spmm_kernel): the
 §8d algorithmic bytes PER ITERATION — `8*nnz (A pairs, read once) +
@@ -24,7 +37,7 @@ iterations on the launch stream. The per-launch accounting (each launch's
 own X operand counted separately; the round-1 headline) is kept as the
 secondary field `achieved_per_launch`. `traffic` is the rocprofv3
 PMC-measured fabric traffic per launch (tools/measure_traffic.py, run
-automatically at N=1 when rocprofv3 is present; ARROW_TRAFFIC_PROBE=0
+by --full at N=1 when rocprofv3 is present; ARROW_TRAFFIC_PROBE=0
 skips, ARROW_TRAFFIC_JSON points at a pre-measured file).
 `cpu_baseline` times the reference's own CPU arithmetic (scipy CSR @,
 arrow_slim_mpi.py:109-144 — restated via oracle semantics) on a bounded
@@ -59,7 +72,22 @@ def build_parser():
     p.add_argument('--device', type=str, default='gpu', choices=['gpu', 'cpu'])
     p.add_argument('--band', type=int, default=1024,
                    help='diagonal-block band half-width (planar-like locality)')
-    p.add_argument('--no-cpu-baseline', action='store_true')
+    p.add_argument('--full', action='store_true',
+                   help='also run the secondary measurements (streaming HBM '
+                        'peak, HIP-event roofline pass, rocprofv3 traffic '
+                        'probe, CPU baseline); a plain run only sets up, '
+                        'warms up, times the steps and prints the result')
+    p.add_argument('--no-cpu-baseline', action='store_true',
+                   help='with --full: skip the CPU baseline leg')
+    p.add_argument('--cpu-baseline-seconds', type=float, default=8.0,
+                   help='with --full: how long each core runs the CPU '
+                        'baseline sample')
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed steps write the result stripe of '
+                        'the last timed step to DIR/C.npy (float32; '
+                        'DIR/C_rank<r>.npy per rank at world>1); at most '
+                        '32 MiB over all ranks: a stripe over its 1/world '
+                        'share is cut to a fixed seeded row sample')
     p.add_argument('--json-out', type=str, default=None)
     p.add_argument('--check', action='store_true',
                    help='parity mode (L=1): run 3 iterations of the exact '
@@ -86,7 +114,14 @@ COL_DEG = 2
 ROW0_DEG = 2
 HUB_ROWS = 16
 HUB_NNZ = 50_000
-VAL_SCALE = 0.55  # keeps ||X|| stable across iterations (sqrt(3/deg_total))
+# Values are positive and every row of the assembled matrix sums to 1 (each
+# block carries a fixed share of its rows' sum, see ROW_SHARE): the
+# iteration X := A X then neither grows nor dies out, so the result stays
+# finite and non-trivial after any number of steps. A signed, unnormalised
+# A grows ~5x per step through the hub rows (measured at the default size:
+# max|C| = 2.2e6 nine steps after |X| <= 1), i.e. overflows f32 near step
+# 55. Only the values differ; the sparsity pattern is the workload.
+ROW_SHARE = {'diag': 0.75, 'col': 0.25, 'row0': 1.0}
 
 
 def _gen_cols(role, w, deg, band, gen, device):
@@ -105,9 +140,9 @@ def _gen_cols(role, w, deg, band, gen, device):
     return torch.sort(cols, dim=1).values
 
 
-def generate_block(role, w, seed, device, band):
+def generate_block(role, w, seed, device, band, share=1.0):
     """Returns (indptr int64, indices int32, data f32) host numpy arrays for
-    one w x w block."""
+    one w x w block. Each row's values are positive and sum to `share`."""
     import torch
     deg = {'diag': DIAG_DEG, 'col': COL_DEG, 'row0': ROW0_DEG}[role]
     gen = torch.Generator(device=device)
@@ -130,15 +165,24 @@ def generate_block(role, w, seed, device, band):
         indptr = torch.arange(0, indices.numel() + 1, deg, dtype=torch.int64,
                               device=device)
     nnz = indices.numel()
-    data = (torch.rand(nnz, generator=gen, device=device) * 2 - 1) * VAL_SCALE
+    data = torch.rand(nnz, generator=gen, device=device) + 0.5
+    # rows are uniform-length runs: the hub head (if any), then the rest
+    hub_rows = HUB_ROWS if nnz > cols.numel() else 0
+    n_head = hub_rows * (HUB_NNZ + deg)
+    runs = [data[n_head:].view(-1, deg)]
+    if hub_rows:
+        runs.append(data[:n_head].view(hub_rows, HUB_NNZ + deg))
+    for rows in runs:
+        rows *= (share / rows.sum(dim=1, keepdim=True,
+                                  dtype=torch.float64)).float()
     return (indptr.cpu().numpy(),
             indices.to(torch.int32).cpu().numpy(),
             data.float().cpu().numpy())
 
 
-def block_csr(role, w, seed, device, band):
+def block_csr(role, w, seed, device, band, share=1.0):
     from scipy import sparse
-    indptr, indices, data = generate_block(role, w, seed, device, band)
+    indptr, indices, data = generate_block(role, w, seed, device, band, share)
     return sparse.csr_matrix((data, indices, indptr), shape=(w, w))
 
 
@@ -155,13 +199,19 @@ def build_blocks_for_rank(rank, world, w, nb, parts, gen_device, band):
     bpr = -(-nb // world)
     first = min(rank * bpr, nb)
     last = min(first + bpr, nb)
+    # the parts' products add up, and block-row 0 is spread over nb blocks
+    sh = {'row0': ROW_SHARE['row0'] / (nb * parts),
+          'diag': ROW_SHARE['diag'] / parts, 'col': ROW_SHARE['col'] / parts}
     for p in range(parts):
         grid = [[None] * nb for _ in range(nb)]
         for c in range(first, last):
-            grid[0][c] = block_csr('row0', w, 10_000 * p + 10 * c + 1, gen_device, band)
+            grid[0][c] = block_csr('row0', w, 10_000 * p + 10 * c + 1,
+                                   gen_device, band, sh['row0'])
         for r in range(max(first, 1), last):
-            grid[r][r] = block_csr('diag', w, 10_000 * p + 10 * r + 2, gen_device, band)
-            grid[r][0] = block_csr('col', w, 10_000 * p + 10 * r + 3, gen_device, band)
+            grid[r][r] = block_csr('diag', w, 10_000 * p + 10 * r + 2,
+                                   gen_device, band, sh['diag'])
+            grid[r][0] = block_csr('col', w, 10_000 * p + 10 * r + 3,
+                                   gen_device, band, sh['col'])
         grids.append(grid)
     return grids, first, last
 
@@ -214,7 +264,7 @@ def _cpu_worker(args):
 _CPU_BLOCKS = None
 
 
-def cpu_baseline_sample(w, band, k, threads=None):
+def cpu_baseline_sample(w, band, k, threads=None, seconds=8.0):
     """Time the reference CPU arithmetic (scipy CSR @ dense,
     arrow_slim_mpi.py:109-144) on ALL host cores: every core runs the same
     bounded sample (one diagonal block + one hub row-0 block of this
@@ -228,7 +278,6 @@ def cpu_baseline_sample(w, band, k, threads=None):
     A_diag = block_csr('diag', cap_w, 2, 'cpu', band)
     A_row0 = block_csr('row0', cap_w, 1, 'cpu', band)
     _CPU_BLOCKS = (A_diag, A_row0)
-    seconds = 8.0
     jobs = [(seconds, k, 100 + i) for i in range(threads)]
     t0 = time.perf_counter()
     if threads == 1:
@@ -324,14 +373,16 @@ def parity_check(arrow, comm, w, nb, k, band, use_gpu, world):
     X_full = np.concatenate(stripes)
     rows_l, cols_l, data_l = [], [], []
     for c in range(nb):
-        ip, ix, dv = generate_block('row0', w, 10 * c + 1, gen_device, band)
+        ip, ix, dv = generate_block('row0', w, 10 * c + 1, gen_device, band,
+                                    ROW_SHARE['row0'] / nb)
         rows_l.append(np.repeat(np.arange(w), np.diff(ip)))
         cols_l.append(ix.astype(np.int64) + c * w)
         data_l.append(dv)
     for r in range(1, nb):
         for role, seed, coff in (('diag', 10 * r + 2, r * w),
                                  ('col', 10 * r + 3, 0)):
-            ip, ix, dv = generate_block(role, w, seed, gen_device, band)
+            ip, ix, dv = generate_block(role, w, seed, gen_device, band,
+                                        ROW_SHARE[role])
             rows_l.append(np.repeat(np.arange(w), np.diff(ip)) + r * w)
             cols_l.append(ix.astype(np.int64) + coff)
             data_l.append(dv)
@@ -393,6 +444,30 @@ def measure_hbm_peak(reps=10, gib=2.0):
     return round(peak, 1)
 
 
+DUMP_MAX_BYTES = 32 << 20  # all ranks' files together; each gets 1/world
+
+
+def dump_outputs(out_dir, eng0, rank, world):
+    """Write what the timed path handed back in its last step — this rank's
+    result stripe C (== the next iteration's X) — as float32 .npy. A stripe
+    over this rank's share of DUMP_MAX_BYTES (1/world of it, so the files of
+    one run never exceed it together) is cut to a fixed, seeded sample of
+    distinct rows (same rows every run, so two builds compare row for
+    row)."""
+    import torch
+    eng0._flush_x0_pipeline()  # drain a deferred C_0 collective + head copy
+    C = eng0.feature_tile()
+    n, k = C.shape
+    m = max(1, DUMP_MAX_BYTES // max(world, 1) // (4 * k))
+    if n > m:
+        rows = np.sort(np.random.default_rng(2024).choice(n, m, replace=False))
+        C = C[torch.from_numpy(rows).to(C.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    name = 'C' if world <= 1 else f'C_rank{rank}'
+    np.save(os.path.join(out_dir, name + '.npy'),
+            C.detach().cpu().numpy().astype(np.float32, copy=False))
+
+
 def main():
     args = build_parser().parse_args()
     import torch
@@ -431,7 +506,7 @@ def main():
     gen_device = 'cuda' if use_gpu else 'cpu'
 
     hbm_peak_meas = None
-    if use_gpu and rank == 0 and world <= 1 and not args.check:
+    if args.full and use_gpu and rank == 0 and world <= 1 and not args.check:
         hbm_peak_meas = measure_hbm_peak()
         print(f"# measured streaming HBM peak: {hbm_peak_meas} GB/s "
               f"(spec 8000)", file=sys.stderr)
@@ -485,7 +560,9 @@ def main():
         g.manual_seed(42 + comm.rank)
         X = torch.rand(eng0.X_i.shape, generator=g, device='cuda') * 2 - 1
     else:
-        X = torch.rand(eng0.X_i.shape) * 2 - 1
+        g = torch.Generator()
+        g.manual_seed(42 + comm.rank)
+        X = torch.rand(eng0.X_i.shape, generator=g) * 2 - 1
     eng0.set_features(X)
 
     def sync():
@@ -500,26 +577,26 @@ def main():
     use_graph = use_gpu and (args.graph == 'on'
                              or (args.graph == 'auto' and world <= 1))
     steps = args.steps
-    if use_graph and steps % 2 == 1:
-        steps += 1  # the ping-pong X<->C period is 2 steps (see below)
 
     for _ in range(args.warmup):
         one_step()
     sync()
 
-    # roofline instrumentation pass (HIP events on the launch stream; kept
-    # OUTSIDE the timed region so the timed loop is uninstrumented)
+    # roofline instrumentation pass (--full; HIP events on the launch
+    # stream; kept OUTSIDE the timed region so the timed loop is
+    # uninstrumented)
     events = []
-    for eng in arrow.engines:
-        eng.kernel_events = events
-    for _ in range(2):
-        one_step()
-    sync()
-    for eng in arrow.engines:
-        eng.kernel_events = None
+    if args.full:
+        for eng in arrow.engines:
+            eng.kernel_events = events
+        for _ in range(2):
+            one_step()
+        sync()
+        for eng in arrow.engines:
+            eng.kernel_events = None
 
     graph = None
-    if use_graph:
+    if use_graph and steps >= 2:
         # hipGraph-captured steady-state iteration (BASELINE cfg5). One
         # capture spans TWO steps: the X<->C ping-pong returns to its
         # original buffer assignment after a pair, so a replay is exactly
@@ -536,6 +613,10 @@ def main():
     if graph is not None:
         for _ in range(steps // 2):
             graph.replay()
+        if steps % 2:
+            # a replay leaves the ping-pong where the capture started, so
+            # an odd --steps ends on one plain step: exactly `steps` timed
+            one_step()
     else:
         for _ in range(steps):
             one_step()
@@ -547,6 +628,10 @@ def main():
                        device='cuda' if (world > 1 and use_gpu) else 'cpu')
     comm.allreduce_max_(t_t)
     elapsed = float(t_t.item())
+
+    used_graph = graph is not None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng0, comm.rank, comm.size)
 
     nnz_total = expected_nnz(w, nb) * L
     flops = 2.0 * nnz_total * k * steps
@@ -605,8 +690,9 @@ def main():
             roofline["frac_measured"] = round(achieved / hbm_peak_meas, 4)
 
     cpu_base = None
-    if rank == 0 and world <= 1 and not args.no_cpu_baseline:
-        cpu_base = cpu_baseline_sample(w, args.band, k)
+    if args.full and rank == 0 and world <= 1 and not args.no_cpu_baseline:
+        cpu_base = cpu_baseline_sample(w, args.band, k,
+                                       seconds=args.cpu_baseline_seconds)
 
     if (roofline is not None and roofline.get('traffic') is None
             and rank == 0 and world <= 1):
@@ -646,7 +732,7 @@ def main():
                 "rows": args.rows, "width": w, "n_blocks": nb, "parts": L,
                 "features": k, "nnz": nnz_total, "band": args.band,
                 "parallelism": f"block-rows over {n_gpus} GPU(s), RCCL/xGMI",
-                "hipgraph": bool(use_graph),
+                "hipgraph": used_graph,
             },
             "roofline": roofline,
             "cpu_baseline": cpu_base,

@@ -78,13 +78,17 @@ class FakeComm:
         self.sends.append((int(dest), int(tag), np.array(buf, copy=True)))
 
 
-def main():
-    _install_stubs()
-    sys.path.insert(0, REFERENCE)
+def main(inputs_only=False):
+    """inputs_only=True builds only the arrays this repository generates
+    itself (the seeded inputs handed to the reference functions), imports
+    nothing from the reference, writes nothing and returns them."""
     sys.path.insert(0, REPO)
-    from arrow import arrow_dec_mpi  # noqa: reference import (stubbed deps)
-    from arrow.common import graphio as ref_graphio
-    ADM = arrow_dec_mpi.ArrowDecompositionMPI
+    if not inputs_only:
+        _install_stubs()
+        sys.path.insert(1, REFERENCE)
+        from arrow import arrow_dec_mpi  # noqa: reference import (stubbed deps)
+        from arrow.common import graphio as ref_graphio
+        ADM = arrow_dec_mpi.ArrowDecompositionMPI
 
     from arrow_matrix_amd import graphio as my_graphio
     from arrow_matrix_amd import synth
@@ -110,9 +114,11 @@ def main():
             vals[rng.integers(0, rpr, size=max(1, rpr // 4))] = 2 * rpr * total  # sentinel
         cases.append((vals.astype(np.int64), rpr, int(rng.integers(1, 20)), total, off))
     for ci, (p, r, c, t, o) in enumerate(cases):
-        counts, displs, sp, ap = ADM._all_to_all_tables(np.asarray(p), r, c, t, o)
         out[f'a2a_{ci}_in_perm'] = np.asarray(p)
         out[f'a2a_{ci}_meta'] = np.asarray([r, c, t, o])
+        if inputs_only:
+            continue
+        counts, displs, sp, ap = ADM._all_to_all_tables(np.asarray(p), r, c, t, o)
         out[f'a2a_{ci}_counts'] = np.asarray(counts)
         out[f'a2a_{ci}_displs'] = np.asarray(displs)
         out[f'a2a_{ci}_send_perm'] = np.asarray(sp)
@@ -138,6 +144,8 @@ def main():
     for ci, (m, w) in enumerate(nb_cases):
         out[f'nb_{ci}_nnz_per_row'] = np.asarray(m.getnnz(1))
         out[f'nb_{ci}_width'] = np.asarray([w])
+        if inputs_only:
+            continue
         out[f'nb_{ci}_result'] = np.asarray([ADM.number_of_blocks(m, w)])
     out['nb_n_cases'] = np.asarray([len(nb_cases)])
 
@@ -149,9 +157,11 @@ def main():
                                             format='csr'), dtype=np.float32)
         sp_cases.append((m, bs))
     for ci, (m, bs) in enumerate(sp_cases):
-        blocks = ref_graphio.split_matrix_to_blocks(m, bs)
         out[f'split_{ci}_dense'] = m.toarray()
         out[f'split_{ci}_bs'] = np.asarray([bs])
+        if inputs_only:
+            continue
+        blocks = ref_graphio.split_matrix_to_blocks(m, bs)
         out[f'split_{ci}_grid'] = np.asarray([len(blocks), len(blocks[0])])
         for i in range(len(blocks)):
             for j in range(len(blocks[0])):
@@ -174,6 +184,11 @@ def main():
     ]
     for ci, cfg in enumerate(loader_cases):
         banded = cfg.get('banded', False)
+        out[f'load_{ci}_meta'] = np.asarray([cfg['width'], len(cfg['n_blocks']),
+                                             int(cfg['one_based']), cfg['seed'],
+                                             int(banded)])
+        if inputs_only:
+            continue
         decomp = synth.synth_arrow_decomposition(cfg['width'], cfg['n_blocks'],
                                                  avg_deg=4, seed=cfg['seed'],
                                                  block_diagonal=not banded)
@@ -190,9 +205,6 @@ def main():
                 comm, prefix, cfg['width'], is_block_diagonal=not banded,
                 slim=not banded, use_npy=True, use_mmap=False)
         out[f'load_{ci}_n_blocks'] = np.asarray(n_blocks)
-        out[f'load_{ci}_meta'] = np.asarray([cfg['width'], len(cfg['n_blocks']),
-                                             int(cfg['one_based']), cfg['seed'],
-                                             int(banded)])
         if to_next0 is not None:
             out[f'load_{ci}_rank0_to_next'] = to_next0
         # rank-0's own blocks (row 0 of part 0: A_00 only in slim scatter)
@@ -232,7 +244,8 @@ def main():
         def Barrier(self):
             pass
 
-    from arrow import matrix_slice as ref_ms
+    if not inputs_only:
+        from arrow import matrix_slice as ref_ms
     ms_cases = []
     for t in range(4):
         nn = int(rng.integers(6, 40))
@@ -242,8 +255,10 @@ def main():
                                             format='csr'), dtype=np.float32)
         ms_cases.append(m)
     for ci, m in enumerate(ms_cases):
-        ms = ref_ms.MatrixSlice.initialize(FakeComm1(), m.copy())
         out[f'ms_{ci}_dense'] = m.toarray()
+        if inputs_only:
+            continue
+        ms = ref_ms.MatrixSlice.initialize(FakeComm1(), m.copy())
         out[f'ms_{ci}_local'] = ms.A_i_local.toarray()
         out[f'ms_{ci}_x_index_in'] = np.asarray(ms.x_index_in)
         out[f'ms_{ci}_rank_in'] = np.asarray(ms.rank_in)
@@ -253,6 +268,8 @@ def main():
         out[f'ms_{ci}_recv_count'] = np.asarray(ms.recv_count)
         out[f'ms_{ci}_bounds'] = np.asarray([ms.start_col, ms.end_col])
     out['ms_n_cases'] = np.asarray([len(ms_cases)])
+    if inputs_only:
+        return out
 
     path = os.environ.get('ARROW_GOLDEN_OUT',
                           os.path.join(HERE, 'reference_katsets.npz'))

@@ -31,7 +31,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_pass(counters, outdir, bench_args):
     # ARROW_TRAFFIC_CHILD stops the bench child from launching its own
-    # traffic probe (bench.py runs this script automatically at N=1)
+    # traffic probe (bench.py --full runs this script at N=1)
     env = dict(os.environ, TMPDIR='/tmp', ARROW_TRAFFIC_CHILD='1')
     cmd = ['rocprofv3', '--pmc', *counters, '--kernel-include-regex',
            'spmm_kernel', '-d', outdir, '--',
