@@ -40,7 +40,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1001  // round 2: set_qblocks, create_opts flags bit 2, wave-grab scheduler
+#define ARROW_ABI_VERSION 1002  // arrow_spmm_plan (launch-plan query)
 
 namespace {
 
@@ -82,20 +82,6 @@ struct CsrBlock {
   int32_t *qctr = nullptr;  // device, 8 chunk counters padded 32 ints apart
   int q_blocks = 0;         // per-structure grid override (0 = ARROW_Q_BLOCKS)
 };
-
-int env_queue_default() {
-  // -1 unset (per-launch policy: queue when GROUP >= 8 — measured
-  // +54 % at k=128/cfg4, +18 % at k=64, +2 % at k=32 same-box, but
-  // -19 % at k=16 where the per-chunk barrier dominates 4-lane groups;
-  // profiles/r01_queue_chunk_sweep.txt, r01_ksweep_queue_20M.txt);
-  // ARROW_QUEUE=0 forces grid-stride, ARROW_QUEUE=1 forces queues.
-  static const int v = [] {
-    const char *e = getenv("ARROW_QUEUE");
-    if (!e || !e[0]) return -1;
-    return (e[0] == '0') ? 0 : 1;
-  }();
-  return v;
-}
 
 std::unordered_map<int64_t, CsrBlock> g_blocks;
 int64_t g_next_handle = 1;
@@ -605,89 +591,141 @@ int launch_route(RouteOp op, float *dst, const float *src, const int64_t *idx,
 // SpMM dispatch over (VEC, GROUP, BETA, GUARD)
 // ---------------------------------------------------------------------------
 
-struct LaunchCfg {
-  int vec;
-  int group;
-  int64_t col_span;  // columns covered per launch = group * vec
-};
-
-LaunchCfg pick_cfg(int64_t k) {
-  static const int g64 =
-      [] { const char *e = getenv("ARROW_SPMM_G64");
-           return (e && e[0] == '1') ? 1 : 0; }();
-  if (g64 && k == 128) return {2, 64, 128};  // A/B: wave-wide groups, float2
-  static const int k16g8 =
-      [] { const char *e = getenv("ARROW_K16_G8");
-           return (e && e[0] == '1') ? 1 : 0; }();
-  if (k16g8 && k == 16) return {2, 8, 16};  // A/B: float2 x 8 lanes,
-                                            // block-grab queue eligible
-  int vec = (k % 4 == 0) ? 4 : (k % 2 == 0) ? 2 : 1;
-  int64_t lanes_needed = (k + vec - 1) / vec;
-  int group = 1;
-  while (group < lanes_needed && group < 64) group <<= 1;
-  return {vec, group, (int64_t)group * vec};
-}
-
-template <int VEC, int GROUP>
-int launch_spmm_vg(const CsrBlock &blk, const float *X0, const float *X1,
-                   float *C, int64_t k, int beta, hipStream_t stream) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
+// Kernel-tuning environment, read ONCE per process on first use (first
+// arrow_spmm / arrow_spmm_dual / arrow_spmm_plan call). Changing a variable
+// afterwards has no effect.
+struct SpmmEnv {
+  int g64;        // ARROW_SPMM_G64=1: k=128 as float2 x 64 lanes (A/B)
+  int k16g8;      // ARROW_K16_G8=1: k=16 as float2 x 8 lanes (A/B, block-grab
+                  // queue eligible)
   // Non-temporal pairs load + C store: default ON (+1.4-1.7 % at cfg4
   // with the queue scheduler — the once-read A stream and once-written C
   // stop evicting the X window; profiles/r01_nt_chunk_k32_ab.txt,
   // r01_colsort_nt_ab.txt). ARROW_SPMM_NT=0 restores cached accesses.
-  static const int nt_mode = [] {
-    const char *e = getenv("ARROW_SPMM_NT");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  const int qd = blk.queue_mode >= 0 ? blk.queue_mode : env_queue_default();
+  int nt_mode;
+  // ARROW_QUEUE: -1 unset (per-launch policy below), 0 forces grid-stride,
+  // 1 forces queues.
+  int queue_default;
   // Per-wave queue grabs (spmm_kernel_qw): no per-chunk block barrier.
-  // Default AUTO: wave variant at GROUP < 8 (k=16: measured +10% over the
-  // fused grid-stride and +15% over the round-1 baseline,
+  // Default AUTO (-1): wave variant at GROUP < 8 (k=16: measured +10% over
+  // the fused grid-stride and +15% over the round-1 baseline,
   // profiles/r02_ab2_sweep.log k16_fused_q1_qw), block variant at
   // GROUP >= 8 (k=128: wave measured -17%, r02_ab1). ARROW_QWAVE=0/1
   // forces.
-  static const int qwave_env = [] {
-    const char *e = getenv("ARROW_QWAVE");
-    if (!e || !e[0]) return -1;
-    return (e[0] == '1') ? 1 : 0;
-  }();
-  const bool qwave = qwave_env >= 0 ? (qwave_env == 1) : (GROUP < 8);
+  int qwave;
   // policy default: queues need GROUP >= 4 AND enough work per structure —
   // below ~32M nnz (ARROW_Q_MIN_NNZ overrides) the per-grab overhead
-  // outweighs the L2 window benefit
-  static const int64_t q_min_nnz = [] {
-    const char *e = getenv("ARROW_Q_MIN_NNZ");
-    return e ? (int64_t)atoll(e) : (32LL << 20);
-  }();
-  const bool useq = blk.qseg &&
-      (qd >= 0 ? qd : (GROUP >= 4 && blk.nnz >= q_min_nnz));
+  // outweighs the L2 window benefit (measured +54 % at k=128/cfg4, +18 %
+  // at k=64, +2 % at k=32 same-box; profiles/r01_queue_chunk_sweep.txt,
+  // r01_ksweep_queue_20M.txt)
+  int64_t q_min_nnz;
   // Queue mode: size the grid to residency (8 blocks/CU fit at this
   // occupancy — 4 waves/WG, 8 waves/SIMD), not to the item count; chunk =
   // 4 rounds per grab (measured best on the fused cfg4 structure: 1/2/4 →
   // 4306/4450/4552 GF/s, profiles/r02_ab2_sweep.log).
-  static const int q_chunk_mult = [] {
-    const char *e = getenv("ARROW_Q_CHUNK");
-    return e ? std::max(1, atoi(e)) : 4;
-  }();
-  static const int q_blocks_env = [] {
-    const char *e = getenv("ARROW_Q_BLOCKS");
-    return e ? std::max(8, atoi(e)) : 2048;
-  }();
-  const int q_blocks = blk.q_blocks > 0 ? blk.q_blocks : q_blocks_env;
-  const int chunk_items = GROUPS_PER_BLOCK * q_chunk_mult;
+  int q_chunk_mult;  // ARROW_Q_CHUNK
+  int q_blocks;      // ARROW_Q_BLOCKS
   // per-wave grabs pull GROUPS_PER_WAVE-item rounds. Default 2 rounds —
   // the wave variant regresses at larger grabs (k=16: 1811 GF/s at 2 vs
   // 1342 at 4, 786 at 8 — its locality window is per-wave, so bigger
   // chunks smear it). ARROW_QW_CHUNK overrides.
-  static const int qw_chunk_mult = [] {
-    const char *e = getenv("ARROW_QW_CHUNK");
-    return e ? std::max(1, atoi(e)) : 2;
+  int qw_chunk_mult;
+};
+
+const SpmmEnv &spmm_env() {
+  static const SpmmEnv env = [] {
+    SpmmEnv v;
+    const char *e = getenv("ARROW_SPMM_G64");
+    v.g64 = (e && e[0] == '1') ? 1 : 0;
+    e = getenv("ARROW_K16_G8");
+    v.k16g8 = (e && e[0] == '1') ? 1 : 0;
+    e = getenv("ARROW_SPMM_NT");
+    v.nt_mode = (e && e[0] == '0') ? 0 : 1;
+    e = getenv("ARROW_QUEUE");
+    v.queue_default = (!e || !e[0]) ? -1 : (e[0] == '0') ? 0 : 1;
+    e = getenv("ARROW_QWAVE");
+    v.qwave = (!e || !e[0]) ? -1 : (e[0] == '1') ? 1 : 0;
+    e = getenv("ARROW_Q_MIN_NNZ");
+    v.q_min_nnz = e ? (int64_t)atoll(e) : (32LL << 20);
+    e = getenv("ARROW_Q_CHUNK");
+    v.q_chunk_mult = e ? std::max(1, atoi(e)) : 4;
+    e = getenv("ARROW_Q_BLOCKS");
+    v.q_blocks = e ? std::max(8, atoi(e)) : 2048;
+    e = getenv("ARROW_QW_CHUNK");
+    v.qw_chunk_mult = e ? std::max(1, atoi(e)) : 2;
+    return v;
   }();
-  const int chunk_items_w = (64 / GROUP) * qw_chunk_mult;
+  return env;
+}
+
+enum Scheduler { SCHED_GRID_STRIDE = 0, SCHED_QUEUE_BLOCK = 1, SCHED_QUEUE_WAVE = 2 };
+constexpr int GRID_STRIDE_MAX_BLOCKS = 8192;
+
+// The whole launch decision for one arrow_spmm call. launch_spmm_vg consumes
+// it; arrow_spmm_plan exports it.
+struct SpmmPlan {
+  int vec;
+  int group;
+  int scheduler;    // Scheduler
+  int nt_mode;
+  int chunk_items;  // items per queue grab as launched (0 for grid-stride)
+  int grid_cap;     // max workgroups for the chosen scheduler
+  int n_launches;   // col_off launches = ceil(k / (group * vec))
+};
+
+void pick_cfg(int64_t k, int *vec_out, int *group_out) {
+  const SpmmEnv &env = spmm_env();
+  if (env.g64 && k == 128) { *vec_out = 2; *group_out = 64; return; }
+  if (env.k16g8 && k == 16) { *vec_out = 2; *group_out = 8; return; }
+  int vec = (k % 4 == 0) ? 4 : (k % 2 == 0) ? 2 : 1;
+  int64_t lanes_needed = (k + vec - 1) / vec;
+  int group = 1;
+  while (group < lanes_needed && group < 64) group <<= 1;
+  *vec_out = vec;
+  *group_out = group;
+}
+
+// queue_mode: the structure's arrow_csr_set_queue mode (-1 follows
+// ARROW_QUEUE); q_blocks_override: its arrow_csr_set_qblocks value (0 = none).
+SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
+                   int q_blocks_override) {
+  const SpmmEnv &env = spmm_env();
+  SpmmPlan p;
+  pick_cfg(k, &p.vec, &p.group);
+  p.nt_mode = env.nt_mode;
+  const int qd = queue_mode >= 0 ? (queue_mode ? 1 : 0) : env.queue_default;
+  const bool useq = qd >= 0 ? (qd == 1)
+                            : (p.group >= 4 && nnz >= env.q_min_nnz);
+  const bool qwave = env.qwave >= 0 ? (env.qwave == 1) : (p.group < 8);
+  if (!useq) {
+    p.scheduler = SCHED_GRID_STRIDE;
+    p.chunk_items = 0;
+    p.grid_cap = GRID_STRIDE_MAX_BLOCKS;
+  } else {
+    p.scheduler = qwave ? SCHED_QUEUE_WAVE : SCHED_QUEUE_BLOCK;
+    p.chunk_items = qwave ? (64 / p.group) * env.qw_chunk_mult
+                          : (BLOCK_THREADS / p.group) * env.q_chunk_mult;
+    p.grid_cap = q_blocks_override > 0 ? q_blocks_override : env.q_blocks;
+  }
+  const int64_t span = (int64_t)p.group * p.vec;
+  p.n_launches = (int)((k + span - 1) / span);
+  return p;
+}
+
+template <int VEC, int GROUP>
+int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
+                   const float *X1, float *C, int64_t k, int beta,
+                   hipStream_t stream) {
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
+  const int nt_mode = plan.nt_mode;
+  const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
+  const bool qwave = plan.scheduler == SCHED_QUEUE_WAVE;
+  if (useq && !(blk.qseg && blk.qctr)) {
+    set_error("arrow_spmm: structure has no queue segments");
+    return -1;
+  }
   int blocks = (int)std::min<int64_t>(
-      (blk.n_items + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK,
-      useq ? q_blocks : 8192);
+      (blk.n_items + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK, plan.grid_cap);
   if (blocks < 1) blocks = 1;
   const int64_t span = (int64_t)GROUP * VEC;
   for (int64_t col_off = 0; col_off < k; col_off += span) {
@@ -708,18 +746,18 @@ int launch_spmm_vg(const CsrBlock &blk, const float *X0, const float *X1,
       HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
       if (qwave) {
         if (beta == 0) {
-          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 0, true>, chunk_items_w);
-          else       runq(spmm_kernel_qw<VEC, GROUP, 0, false>, chunk_items_w);
+          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 0, true>, plan.chunk_items);
+          else       runq(spmm_kernel_qw<VEC, GROUP, 0, false>, plan.chunk_items);
         } else {
-          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 1, true>, chunk_items_w);
-          else       runq(spmm_kernel_qw<VEC, GROUP, 1, false>, chunk_items_w);
+          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 1, true>, plan.chunk_items);
+          else       runq(spmm_kernel_qw<VEC, GROUP, 1, false>, plan.chunk_items);
         }
       } else if (beta == 0) {
-        if (guard) runq(spmm_kernel_q<VEC, GROUP, 0, true>, chunk_items);
-        else       runq(spmm_kernel_q<VEC, GROUP, 0, false>, chunk_items);
+        if (guard) runq(spmm_kernel_q<VEC, GROUP, 0, true>, plan.chunk_items);
+        else       runq(spmm_kernel_q<VEC, GROUP, 0, false>, plan.chunk_items);
       } else {
-        if (guard) runq(spmm_kernel_q<VEC, GROUP, 1, true>, chunk_items);
-        else       runq(spmm_kernel_q<VEC, GROUP, 1, false>, chunk_items);
+        if (guard) runq(spmm_kernel_q<VEC, GROUP, 1, true>, plan.chunk_items);
+        else       runq(spmm_kernel_q<VEC, GROUP, 1, false>, plan.chunk_items);
       }
     } else if (beta == 0) {
       if (guard) run(spmm_kernel<VEC, GROUP, 0, true>);
@@ -734,16 +772,17 @@ int launch_spmm_vg(const CsrBlock &blk, const float *X0, const float *X1,
 }
 
 template <int VEC>
-int launch_spmm_v(const CsrBlock &blk, const float *X0, const float *X1,
-                  float *C, int64_t k, int beta, int group, hipStream_t stream) {
-  switch (group) {
-    case 1:  return launch_spmm_vg<VEC, 1>(blk, X0, X1, C, k, beta, stream);
-    case 2:  return launch_spmm_vg<VEC, 2>(blk, X0, X1, C, k, beta, stream);
-    case 4:  return launch_spmm_vg<VEC, 4>(blk, X0, X1, C, k, beta, stream);
-    case 8:  return launch_spmm_vg<VEC, 8>(blk, X0, X1, C, k, beta, stream);
-    case 16: return launch_spmm_vg<VEC, 16>(blk, X0, X1, C, k, beta, stream);
-    case 32: return launch_spmm_vg<VEC, 32>(blk, X0, X1, C, k, beta, stream);
-    default: return launch_spmm_vg<VEC, 64>(blk, X0, X1, C, k, beta, stream);
+int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
+                  const float *X1, float *C, int64_t k, int beta,
+                  hipStream_t stream) {
+  switch (plan.group) {
+    case 1:  return launch_spmm_vg<VEC, 1>(blk, plan, X0, X1, C, k, beta, stream);
+    case 2:  return launch_spmm_vg<VEC, 2>(blk, plan, X0, X1, C, k, beta, stream);
+    case 4:  return launch_spmm_vg<VEC, 4>(blk, plan, X0, X1, C, k, beta, stream);
+    case 8:  return launch_spmm_vg<VEC, 8>(blk, plan, X0, X1, C, k, beta, stream);
+    case 16: return launch_spmm_vg<VEC, 16>(blk, plan, X0, X1, C, k, beta, stream);
+    case 32: return launch_spmm_vg<VEC, 32>(blk, plan, X0, X1, C, k, beta, stream);
+    default: return launch_spmm_vg<VEC, 64>(blk, plan, X0, X1, C, k, beta, stream);
   }
 }
 
@@ -1026,12 +1065,26 @@ int arrow_spmm_dual(int64_t handle, const float *X0_dev, const float *X1_dev,
     HIP_CHECK(hipGetLastError());
   }
 
-  const LaunchCfg cfg = pick_cfg(k);
-  switch (cfg.vec) {
-    case 4: return launch_spmm_v<4>(blk, X0_dev, X1_dev, C_dev, k, beta, cfg.group, stream);
-    case 2: return launch_spmm_v<2>(blk, X0_dev, X1_dev, C_dev, k, beta, cfg.group, stream);
-    default: return launch_spmm_v<1>(blk, X0_dev, X1_dev, C_dev, k, beta, cfg.group, stream);
+  const SpmmPlan plan = spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks);
+  switch (plan.vec) {
+    case 4: return launch_spmm_v<4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
+    case 2: return launch_spmm_v<2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
+    default: return launch_spmm_v<1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
   }
+}
+
+int arrow_spmm_plan(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                    int n_out) {
+  if (k <= 0 || nnz < 0 || !out || n_out < 0) {
+    set_error("arrow_spmm_plan: bad arguments");
+    return -1;
+  }
+  const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0);
+  const int32_t fields[ARROW_PLAN_FIELDS] = {
+      p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
+      p.n_launches};
+  for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
+  return ARROW_PLAN_FIELDS;
 }
 
 int arrow_spmm(int64_t handle, const float *X_dev, float *C_dev, int64_t k,

@@ -68,6 +68,10 @@ def _load():
                                     ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
     lib.arrow_spmm_dual.restype = ctypes.c_int
+    lib.arrow_spmm_plan.argtypes = [ctypes.c_int64, ctypes.c_int64,
+                                    ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
+                                    ctypes.c_int]
+    lib.arrow_spmm_plan.restype = ctypes.c_int
     for name in ('arrow_gather_rows_f32', 'arrow_scatter_rows_f32',
                  'arrow_scatter_add_rows_f32'):
         fn = getattr(lib, name)
@@ -213,6 +217,24 @@ def permute_add_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream=0)
     _check(_load().arrow_permute_add_rows_f32(dst_ptr, src_ptr, dst_idx_ptr,
                                               src_idx_ptr, n, k, stream),
            "arrow_permute_add_rows_f32")
+
+
+PLAN_FIELDS = ('vec', 'group', 'scheduler', 'nt_mode', 'chunk_items',
+               'grid_cap', 'launches')
+SCHED_GRID_STRIDE, SCHED_QUEUE_BLOCK, SCHED_QUEUE_WAVE = 0, 1, 2
+
+
+def spmm_plan(k: int, nnz: int, queue_mode: int = -1) -> dict:
+    """The launch plan arrow_spmm takes for a structure of `nnz` nonzeros at
+    width k (arrow_spmm_plan; needs no device). The ARROW_* kernel-tuning
+    variables are read once per process, on first use."""
+    out = (ctypes.c_int32 * len(PLAN_FIELDS))()
+    n = _check(_load().arrow_spmm_plan(int(k), int(nnz), int(queue_mode), out,
+                                       len(PLAN_FIELDS)), "arrow_spmm_plan")
+    if n != len(PLAN_FIELDS):
+        raise ArrowSpmmError(f"arrow_spmm_plan: library has {n} plan fields, "
+                             f"binding expects {len(PLAN_FIELDS)}")
+    return dict(zip(PLAN_FIELDS, (int(v) for v in out)))
 
 
 def abi_version() -> int:

@@ -96,6 +96,36 @@ int arrow_spmm(int64_t handle, const float *X_dev, float *C_dev, int64_t k,
 int arrow_spmm_dual(int64_t handle, const float *X0_dev, const float *X1_dev,
                     float *C_dev, int64_t k, int beta, void *stream);
 
+/* Launch-plan query: the decision arrow_spmm / arrow_spmm_dual take for a
+ * structure with `nnz` nonzeros at feature width k. Needs no handle and no
+ * device; the launcher itself consumes the same plan. queue_mode is the
+ * structure's arrow_csr_set_queue mode (1 on, 0 off, -1 follow ARROW_QUEUE).
+ * Writes min(n_out, ARROW_PLAN_FIELDS) int32 fields to out, in the order of
+ * the ARROW_PLAN_* indices below, and returns ARROW_PLAN_FIELDS (negative
+ * on error).
+ *
+ * The kernel-tuning environment variables (ARROW_SPMM_G64, ARROW_K16_G8,
+ * ARROW_SPMM_NT, ARROW_QUEUE, ARROW_QWAVE, ARROW_Q_MIN_NNZ, ARROW_Q_CHUNK,
+ * ARROW_Q_BLOCKS, ARROW_QW_CHUNK) are read ONCE per process, on the first
+ * arrow_spmm, arrow_spmm_dual or arrow_spmm_plan call. Setting one later in
+ * the same process changes nothing: choose a variant before first use, in
+ * a fresh process. */
+#define ARROW_PLAN_VEC 0         /* floats per lane: 1, 2 or 4 */
+#define ARROW_PLAN_GROUP 1       /* lanes per work item: 1..64 */
+#define ARROW_PLAN_SCHEDULER 2   /* 0 grid-stride, 1 block-grab queue,
+                                    2 wave-grab queue */
+#define ARROW_PLAN_NT_MODE 3     /* 1 non-temporal A loads / C stores */
+#define ARROW_PLAN_CHUNK_ITEMS 4 /* items per queue grab as launched
+                                    (0 for grid-stride) */
+#define ARROW_PLAN_GRID_CAP 5    /* workgroup cap of the chosen scheduler:
+                                    the queue grid (ARROW_Q_BLOCKS, before
+                                    any arrow_csr_set_qblocks override) or
+                                    the grid-stride cap */
+#define ARROW_PLAN_LAUNCHES 6    /* column-offset launches, ceil(k/(group*vec)) */
+#define ARROW_PLAN_FIELDS 7
+int arrow_spmm_plan(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                    int n_out);
+
 /* dst[i, :] = src[idx[i], :]   (n rows of width k, fp32, device) */
 int arrow_gather_rows_f32(const float *src_dev, float *dst_dev,
                           const int64_t *idx_dev, int64_t n, int64_t k,
