@@ -66,7 +66,8 @@ def bench_spmm(path: Union[str, None],
         return
 
     arrow = ArrowDecompositionMPI.initialize(comm, n_blocks, to_prev, to_next,
-                                             width, n_features, device, blocked, slim)
+                                             width, n_features, device, blocked, slim,
+                                             dtype=datatype)
 
     wb_logging.log({"actual_ranks": comm.size})
     rng = np.random.default_rng(42 + comm.rank)
@@ -74,7 +75,7 @@ def bench_spmm(path: Union[str, None],
 
     tic = time.perf_counter()
     arrow.load_data_from_blocks(blocks)
-    arrow.zero_rhs(width, n_features)
+    arrow.zero_rhs(width, n_features, dtype=datatype)
     comm.barrier()
     wb_logging.log({"init_time": time.perf_counter() - tic})
 

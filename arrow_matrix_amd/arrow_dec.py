@@ -85,20 +85,25 @@ class ArrowDecompositionMPI:
     def initialize(comm: Optional[Comm], n_blocks: np.ndarray,
                    to_prev_permutation, to_next_permutation,
                    rows_per_rank: int, feature_columns: int, device: str = 'cpu',
-                   block_diagonal: bool = True, slim: bool = True):
+                   block_diagonal: bool = True, slim: bool = True,
+                   dtype=np.float32):
         """Factory, keeping the reference's signature
         (arrow_dec_mpi.py:106-177). to_prev/to_next are the per-rank
         permutation slices as returned by load_decomposition_new (lists with
-        one entry per decomposition part)."""
+        one entry per decomposition part). dtype (float32 or float64) is
+        passed to every engine: on the GPU the precision is fixed here, at
+        construction."""
         assert not slim or block_diagonal  # reference arrow_dec_mpi.py:131
         comm = comm if comm is not None else default_comm()
         if slim:
-            engines = [ArrowSlimMPI(comm, tiles_per_side=int(nb), device=device)
+            engines = [ArrowSlimMPI(comm, tiles_per_side=int(nb), device=device,
+                                    dtype=dtype)
                        for nb in n_blocks]
         else:
             from .arrow_mpi import ArrowMPI
             engines = [ArrowMPI(comm, is_block_diagonal=block_diagonal,
-                                tiles_per_side=int(nb), device=device)
+                                tiles_per_side=int(nb), device=device,
+                                dtype=dtype)
                        for nb in n_blocks]
         return ArrowDecompositionMPI(comm, engines, n_blocks, rows_per_rank,
                                      feature_columns, to_prev_permutation,
@@ -217,7 +222,8 @@ class ArrowDecompositionMPI:
                     import torch as _t
                     free, total = _t.cuda.mem_get_info()
                     k = self._n_feature_columns
-                    need = [4 * k * (2 * eng.n_owned * self.width
+                    itemsize = self.engines[0].np_dtype.itemsize
+                    need = [itemsize * k * (2 * eng.n_owned * self.width
                                      + 2 * self.width)
                             for eng in self.engines]
                     # sequential fits only if ALL parts' X/C buffers plus a
@@ -309,10 +315,10 @@ class ArrowDecompositionMPI:
                         np.arange(csr.shape[0], dtype=np.int64),
                         np.diff(csr.indptr)) + br * w)
                     cols_l.append(csr.indices.astype(np.int64) + bc * w)
-                    data_l.append(csr.data.astype(np.float32))
+                    data_l.append(csr.data.astype(eng0.np_dtype))
             rows = np.concatenate(rows_l) if rows_l else np.empty(0, np.int64)
             cols = np.concatenate(cols_l) if cols_l else np.empty(0, np.int64)
-            data = np.concatenate(data_l) if data_l else np.empty(0, np.float32)
+            data = np.concatenate(data_l) if data_l else np.empty(0, eng0.np_dtype)
             nr = R_i[np.clip(rows, 0, None)]
             if fold_cols:
                 nc = M_i[np.clip(cols, 0, None)]

@@ -16,6 +16,8 @@ resident structure. Every rank is a column rank (holds feature tiles).
 """
 from typing import Optional
 
+import numpy as np
+
 from .arrow_slim import ArrowSlimMPI
 from .comm import Comm
 
@@ -24,7 +26,8 @@ class ArrowMPI(ArrowSlimMPI):
 
     def __init__(self, comm: Optional[Comm] = None,
                  is_block_diagonal: bool = False,
-                 tiles_per_side: Optional[int] = None, device: str = 'cpu'):
+                 tiles_per_side: Optional[int] = None, device: str = 'cpu',
+                 dtype=np.float32):
         super().__init__(comm, tiles_per_side=tiles_per_side, device=device,
-                         banded=not is_block_diagonal)
+                         banded=not is_block_diagonal, dtype=dtype)
         self.is_block_diagonal = is_block_diagonal

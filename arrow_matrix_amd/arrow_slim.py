@@ -37,20 +37,27 @@ import time
 class ArrowSlimMPI(ArrowMatrix):
 
     def __init__(self, comm: Optional[Comm] = None, tiles_per_side: Optional[int] = None,
-                 device: str = 'cpu', banded: bool = False):
+                 device: str = 'cpu', banded: bool = False,
+                 dtype=np.float32):
         """:param comm: communicator over this matrix's ranks (None = single
         process). :param tiles_per_side: number of block-rows (n_blocks);
         defaults to comm.size, the reference's one-rank-per-block layout.
         :param banded: arrow-banded decomposition (blocks (r, r±1) carried;
         ±1 halo X exchange per iteration — the ArrowMPI variant,
-        arrow_mpi.py:123-175,211-219)."""
+        arrow_mpi.py:123-175,211-219).
+        :param dtype: float32 or float64. On the GPU the precision is fixed
+        HERE (the resident structures are uploaded at load time, before
+        zero_rhs is called); on the cpu device zero_rhs may still choose it,
+        as in the reference."""
         self.comm = comm if comm is not None else Comm()
         self.banded = banded
         self.column_comm = self.comm
         self.tiles_per_side = tiles_per_side if tiles_per_side is not None else self.comm.size
         assert self.tiles_per_side >= 1
         self.device = device
-        self.backend = make_backend(device)
+        self.backend = make_backend(device, dtype)
+        # the engine's precision (the structure builders cast to it)
+        self.np_dtype = self.backend.np_dtype
 
         # contiguous block span owned by this rank
         bpr = -(-self.tiles_per_side // self.comm.size)
@@ -224,7 +231,7 @@ class ArrowSlimMPI(ArrowMatrix):
             b = b.tocsr()
             rows_cat.append(np.repeat(np.arange(w), np.diff(b.indptr)))
             cols_cat.append(b.indices.astype(np.int64) + j * w)
-            data_cat.append(b.data.astype(np.float32))
+            data_cat.append(b.data.astype(self.np_dtype))
         if fuse_all:
             # single process: block-row 0's reduce is the identity, so the
             # whole matrix fuses into ONE launch writing C in place — the
@@ -279,15 +286,15 @@ class ArrowSlimMPI(ArrowMatrix):
             local = j * w - self._rest_row_offset
             rows_cat.append(local + np.repeat(np.arange(w), np.diff(rr.indptr)))
             cols_cat.append(rr.indices.astype(np.int64) + j * w)
-            data_cat.append(rr.data.astype(np.float32))
+            data_cat.append(rr.data.astype(self.np_dtype))
             if split_col:
                 col_rows.append(local + np.repeat(np.arange(w), np.diff(r0.indptr)))
                 col_cols.append(-(r0.indices.astype(np.int64) + 1))  # -> X_0
-                col_data.append(r0.data.astype(np.float32))
+                col_data.append(r0.data.astype(self.np_dtype))
             else:
                 rows_cat.append(local + np.repeat(np.arange(w), np.diff(r0.indptr)))
                 cols_cat.append(-(r0.indices.astype(np.int64) + 1))  # -> X_0
-                data_cat.append(r0.data.astype(np.float32))
+                data_cat.append(r0.data.astype(self.np_dtype))
             for off, blk in ((-1, lo_list[j]), (1, hi_list[j])):
                 if blk is None:
                     continue
@@ -296,7 +303,7 @@ class ArrowSlimMPI(ArrowMatrix):
                     bb = blk.tocsr()
                     rows_cat.append(local + np.repeat(np.arange(w), np.diff(bb.indptr)))
                     cols_cat.append(bb.indices.astype(np.int64) + (t - self.first_block) * w)
-                    data_cat.append(bb.data.astype(np.float32))
+                    data_cat.append(bb.data.astype(self.np_dtype))
                 elif off < 0:  # boundary vs X_halo_lo
                     self._A_bd_lo = (self.backend.upload_block(blk), local)
                 else:          # boundary vs X_halo_hi
@@ -382,7 +389,8 @@ class ArrowSlimMPI(ArrowMatrix):
         np.cumsum(counts, out=indptr[1:])
         handle = self.backend.upload_arrays(
             (perm_rows.size, n_cols), indptr, cols2.astype(np.int32),
-            data2.astype(np.float32), row_ids=perm_rows.astype(np.int64))
+            data2.astype(self.np_dtype),
+            row_ids=perm_rows.astype(np.int64))
         handle.x_rows = self.width
         return handle
 
@@ -397,7 +405,7 @@ class ArrowSlimMPI(ArrowMatrix):
         np.cumsum(np.bincount(rows, minlength=n_rows), out=indptr[1:])
         handle = self.backend.upload_arrays((n_rows, n_cols), indptr,
                                             cols.astype(np.int32),
-                                            data.astype(np.float32),
+                                            data.astype(self.np_dtype),
                                             col_items=col_items)
         handle.x_rows = x_rows  # algorithmic X rows for the roofline
         return handle
@@ -407,14 +415,24 @@ class ArrowSlimMPI(ArrowMatrix):
     def zero_rhs(self, number_of_rows_per_rank: int, number_of_columns: int,
                  dtype=np.float32) -> None:
         assert number_of_rows_per_rank >= 1 and number_of_columns >= 1
-        if np.dtype(dtype) != np.float32:
+        if self.backend.device == 'cuda':
+            # the reference chooses the dtype at zero_rhs time
+            # (arrow_slim_mpi.py:354); here the resident structures were
+            # uploaded at load time in the engine's precision, so zero_rhs
+            # can only confirm it
+            if np.dtype(dtype) != self.np_dtype:
+                raise TypeError(
+                    f"zero_rhs(dtype={np.dtype(dtype)}) on a GPU engine "
+                    f"built for {self.np_dtype}: the precision of a "
+                    f"GPU engine is fixed when it is constructed — pass "
+                    f"dtype= to ArrowSlimMPI / ArrowMPI / "
+                    f"ArrowDecompositionMPI.initialize")
+        elif np.dtype(dtype) != np.float32:
             # the reference chooses the dtype at zero_rhs time
             # (arrow_slim_mpi.py:354)
-            if self.backend.device == 'cuda':
-                raise NotImplementedError(
-                    "float64 runs on device='cpu' (HIP kernels are fp32)")
             if np.dtype(dtype) != self.backend.np_dtype:
                 self.backend = make_backend(self.device, dtype)
+                self.np_dtype = self.backend.np_dtype
                 self.C_i = self.C_0 = self.X_i = self.X_0 = None
         if self.width is not None and self.nnz_owned:
             # blocks were loaded at a fixed block size; a different width
@@ -425,7 +443,8 @@ class ArrowSlimMPI(ArrowMatrix):
                 f"{self.width} fixed at load time")
         if self.backend.device == 'cuda':
             # loud capacity check BEFORE allocating: the buffer set is
-            # 2 stripes + 2 head tiles (+2 halos banded) of fp32; a k that
+            # 2 stripes + 2 head tiles (+2 halos banded) of the engine's
+            # dtype; a k that
             # busts 288 GB of HBM must fail with a sizing message, not a
             # mid-iteration OOM (VERDICT r1 "missing" #4; the reference's
             # own k-tiling, spmm_petsc.py:323-395, is moot at this
@@ -439,7 +458,8 @@ class ArrowSlimMPI(ArrowMatrix):
                       ('C_0', (w_, k_)), ('X_0', (w_, k_))]
             if self.banded:
                 shapes += [('X_halo_lo', (w_, k_)), ('X_halo_hi', (w_, k_))]
-            need = sum(4 * sh[0] * sh[1] for name, sh in shapes
+            itemsize = self.np_dtype.itemsize
+            need = sum(itemsize * sh[0] * sh[1] for name, sh in shapes
                        if getattr(self, name) is None
                        or tuple(getattr(self, name).shape) != sh)
             if need:

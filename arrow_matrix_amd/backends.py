@@ -74,7 +74,13 @@ class CpuBackend:
 class GpuBackend:
     device = 'cuda'
 
-    def __init__(self, device_index: Optional[int] = None):
+    def __init__(self, device_index: Optional[int] = None, dtype=np.float32):
+        self.np_dtype = np.dtype(dtype)
+        if self.np_dtype not in _TORCH_DTYPE:
+            raise NotImplementedError(
+                f"the HIP kernels compute in float32 or float64, not "
+                f"{self.np_dtype}")
+        self.torch_dtype = _TORCH_DTYPE[self.np_dtype]
         if not torch.cuda.is_available():
             raise hip.ArrowSpmmError(
                 "GPU backend requested but no HIP device is available")
@@ -89,18 +95,18 @@ class GpuBackend:
         return torch.cuda.current_stream(self.device_index).cuda_stream
 
     def zeros(self, shape):
-        return torch.zeros(shape, dtype=torch.float32, device=self.torch_device)
+        return torch.zeros(shape, dtype=self.torch_dtype, device=self.torch_device)
 
     def asarray(self, x) -> torch.Tensor:
         if isinstance(x, torch.Tensor):
-            return x.to(self.torch_device, dtype=torch.float32)
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(self.torch_device)
+            return x.to(self.torch_device, dtype=self.torch_dtype)
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=self.np_dtype)).to(self.torch_device)
 
     def index_tensor(self, idx: np.ndarray) -> torch.Tensor:
         return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.torch_device)
 
     def upload_block(self, csr):
-        return hip.CsrBlockGPU(csr)
+        return hip.CsrBlockGPU(csr, dtype=self.np_dtype)
 
     def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int):
         assert X.is_contiguous() and C.is_contiguous()
@@ -109,7 +115,8 @@ class GpuBackend:
     def upload_arrays(self, shape, indptr, indices, data, row_ids=None,
                       col_items=False) -> hip.CsrBlockGPU:
         return hip.CsrBlockGPU(arrays=(shape, indptr, indices, data),
-                               row_ids=row_ids, col_items=col_items)
+                               row_ids=row_ids, col_items=col_items,
+                               dtype=self.np_dtype)
 
     def spmm_dual(self, block: hip.CsrBlockGPU, X0: torch.Tensor,
                   X1: torch.Tensor, C: torch.Tensor, beta: int):
@@ -118,34 +125,39 @@ class GpuBackend:
                         C.shape[1], beta, self._stream())
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
-        out = torch.empty((idx.shape[0], src.shape[1]), dtype=torch.float32,
+        out = torch.empty((idx.shape[0], src.shape[1]), dtype=self.torch_dtype,
                           device=self.torch_device)
         if idx.shape[0]:
             hip.gather_rows(src.data_ptr(), out.data_ptr(), idx.data_ptr(),
-                            idx.shape[0], src.shape[1], self._stream())
+                            idx.shape[0], src.shape[1], self._stream(),
+                            dtype=self.np_dtype)
         return out
 
     def scatter_rows(self, dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor):
         if idx.shape[0]:
             hip.scatter_rows(dst.data_ptr(), src.data_ptr(), idx.data_ptr(),
-                             idx.shape[0], dst.shape[1], self._stream())
+                             idx.shape[0], dst.shape[1], self._stream(),
+                             dtype=self.np_dtype)
 
     def scatter_add_rows(self, dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor):
         if idx.shape[0]:
             hip.scatter_add_rows(dst.data_ptr(), src.data_ptr(), idx.data_ptr(),
-                                 idx.shape[0], dst.shape[1], self._stream())
+                                 idx.shape[0], dst.shape[1], self._stream(),
+                                 dtype=self.np_dtype)
 
     def permute_rows(self, dst, dst_idx, src, src_idx):
         if dst_idx.shape[0]:
             hip.permute_rows(dst.data_ptr(), src.data_ptr(), dst_idx.data_ptr(),
                              src_idx.data_ptr(), dst_idx.shape[0], dst.shape[1],
-                             self._stream())
+                             self._stream(),
+                             dtype=self.np_dtype)
 
     def permute_add_rows(self, dst, dst_idx, src, src_idx):
         if dst_idx.shape[0]:
             hip.permute_add_rows(dst.data_ptr(), src.data_ptr(),
                                  dst_idx.data_ptr(), src_idx.data_ptr(),
-                                 dst_idx.shape[0], dst.shape[1], self._stream())
+                                 dst_idx.shape[0], dst.shape[1], self._stream(),
+                                 dtype=self.np_dtype)
 
     def synchronize(self):
         torch.cuda.synchronize(self.device_index)
@@ -153,11 +165,12 @@ class GpuBackend:
 
 def make_backend(device: str, dtype=np.float32):
     if device in ('gpu', 'cuda'):
-        if np.dtype(dtype) != np.float32:
+        if np.dtype(dtype) not in _TORCH_DTYPE:
             raise NotImplementedError(
-                "the HIP kernels compute in fp32 (the reference benchmark "
-                "default, arrow_bench.py:21); float64 runs on device='cpu'")
-        return GpuBackend()
+                "the HIP kernels compute in float32 (the reference benchmark "
+                "default, arrow_bench.py:21) or float64, not "
+                f"{np.dtype(dtype)}")
+        return GpuBackend(dtype=dtype)
     if device == 'cpu':
         return CpuBackend(dtype)
     raise ValueError(f"unknown device {device!r} (use 'cpu' or 'gpu')")

@@ -40,7 +40,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1002  // arrow_spmm_plan (launch-plan query)
+#define ARROW_ABI_VERSION 1003  // float64 entry points (arrow_*_f64)
 
 namespace {
 
@@ -66,6 +66,11 @@ struct CsrBlock {
   // into the SECOND feature matrix of arrow_spmm_dual: col = -(idx+1)
   // (the fused diagonal+first-block-column layout).
   int2 *pairs = nullptr;
+  // precision tag, fixed at creation: 32 (pairs above) or 64 (the split
+  // arrays below, 12 B/nnz; pairs stays null)
+  int dtype = 32;
+  int32_t *cols64 = nullptr;
+  double *vals64 = nullptr;
   // work items (device): row (bit31 = atomic), [begin, end) into pairs
   int32_t *item_row = nullptr;
   int32_t *item_begin = nullptr;
@@ -471,6 +476,352 @@ __global__ void zero_rows_kernel(float *__restrict__ C,
 }
 
 // ---------------------------------------------------------------------------
+// float64 SpMM.  The twin of the fp32 path above, kept as separate code so
+// the fp32 instantiations stay exactly as they were. A lane covers VEC
+// doubles of an X row (double2 = one 16-byte load when k is even, the same
+// bytes per lane as the fp32 float4), GROUP lanes cover one work item, and
+// A is resident as SPLIT arrays int32 cols[] + double vals[] (12 B/nnz; a
+// padded 16-byte record would waste a third of the A stream). Accumulation
+// is double fma; split rows add with the hardware f64 global atomic.
+// ---------------------------------------------------------------------------
+
+template <int VEC, int GROUP, int BETA, bool GUARD>
+__device__ __forceinline__ void spmm_process_item_f64(
+    const int32_t *__restrict__ cols, const double *__restrict__ vals,
+    int32_t row_raw, int32_t b, int32_t e,
+    const double *__restrict__ X0, const double *__restrict__ X1,
+    double *__restrict__ C, int64_t k, int64_t col0, bool active,
+    int lane_in_group, int nt_mode) {
+  const int32_t row = row_raw & 0x7fffffff;
+  const bool is_split = row_raw < 0;
+
+  double acc[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[j] = 0.0;
+
+  // One staged nonzero per lane: GROUP (col, val) entries are loaded
+  // cooperatively (a coalesced 4-B and a coalesced 8-B load per GROUP
+  // nonzeros) and broadcast with wave shuffles; the 64-bit value travels
+  // as two 32-bit shuffles.
+  struct Staged { int32_t c, lo, hi; };
+  auto xaddr = [&](const Staged &mine, int u) {
+    const int32_t c = __shfl(mine.c, u, GROUP);
+    return (c < 0 ? X1 + (int64_t)(-c - 1) * k : X0 + (int64_t)c * k) + col0;
+  };
+  auto val = [&](const Staged &mine, int u) {
+    return __hiloint2double(__shfl(mine.hi, u, GROUP),
+                            __shfl(mine.lo, u, GROUP));
+  };
+  auto consume = [&](const Staged &mine, int u) {
+    const double *xr = xaddr(mine, u);
+    const double v = val(mine, u);
+    if (active) {
+      if constexpr (VEC == 2) {
+        const double2 xv = *reinterpret_cast<const double2 *>(xr);
+        acc[0] = fma(v, xv.x, acc[0]);
+        acc[1] = fma(v, xv.y, acc[1]);
+      } else {
+        acc[0] = fma(v, xr[0], acc[0]);
+      }
+    }
+  };
+  // 4 entries at a time, the four X-row loads issued back to back BEFORE
+  // any use (see the fp32 body: in-order issue stalls a rolled loop on each
+  // load's s_waitcnt)
+  auto consume4 = [&](const Staged &mine, int u) {
+    if constexpr (VEC == 2) {
+      const double *p0 = xaddr(mine, u + 0);
+      const double *p1 = xaddr(mine, u + 1);
+      const double *p2 = xaddr(mine, u + 2);
+      const double *p3 = xaddr(mine, u + 3);
+      const double v0 = val(mine, u + 0), v1 = val(mine, u + 1);
+      const double v2 = val(mine, u + 2), v3 = val(mine, u + 3);
+      if (active) {
+        const double2 a0 = *reinterpret_cast<const double2 *>(p0);
+        const double2 a1 = *reinterpret_cast<const double2 *>(p1);
+        const double2 a2 = *reinterpret_cast<const double2 *>(p2);
+        const double2 a3 = *reinterpret_cast<const double2 *>(p3);
+        acc[0] = fma(v0, a0.x, acc[0]); acc[1] = fma(v0, a0.y, acc[1]);
+        acc[0] = fma(v1, a1.x, acc[0]); acc[1] = fma(v1, a1.y, acc[1]);
+        acc[0] = fma(v2, a2.x, acc[0]); acc[1] = fma(v2, a2.y, acc[1]);
+        acc[0] = fma(v3, a3.x, acc[0]); acc[1] = fma(v3, a3.y, acc[1]);
+      }
+    } else {
+      consume(mine, u); consume(mine, u + 1);
+      consume(mine, u + 2); consume(mine, u + 3);
+    }
+  };
+  // 8 loads in flight (a deg-8 power-law row issues its whole X-row load
+  // set before any use)
+  auto consume8 = [&](const Staged &mine, int u) {
+    if constexpr (VEC == 2 && GROUP >= 8) {
+      const double *p[8];
+      double v[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        p[j] = xaddr(mine, u + j);
+        v[j] = val(mine, u + j);
+      }
+      if (active) {
+        double2 a[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          a[j] = *reinterpret_cast<const double2 *>(p[j]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          acc[0] = fma(v[j], a[j].x, acc[0]);
+          acc[1] = fma(v[j], a[j].y, acc[1]);
+        }
+      }
+    } else {
+      consume4(mine, u);
+      consume4(mine, u + 4);
+    }
+  };
+  // non-temporal A-stream loads (each entry is read once by one wave)
+  auto load_stage = [&](int32_t idx) -> Staged {
+    int32_t c;
+    double v;
+    if (nt_mode) {
+      c = __builtin_nontemporal_load(cols + idx);
+      v = __builtin_nontemporal_load(vals + idx);
+    } else {
+      c = cols[idx];
+      v = vals[idx];
+    }
+    return Staged{c, __double2loint(v), __double2hiint(v)};
+  };
+  int32_t base = b;
+  for (; base + GROUP <= e; base += GROUP) {  // full chunks
+    const Staged mine = load_stage(base + lane_in_group);
+    if constexpr (GROUP >= 8) {
+#pragma unroll
+      for (int u = 0; u < GROUP; u += 8) consume8(mine, u);
+    } else if constexpr (GROUP >= 4) {
+#pragma unroll
+      for (int u = 0; u < GROUP; u += 4) consume4(mine, u);
+    } else {
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) consume(mine, u);
+    }
+  }
+  if (base < e) {  // remainder (< GROUP entries)
+    const int32_t t = base + lane_in_group;
+    Staged mine{0, 0, 0};
+    if (t < e) {
+      const double v = vals[t];
+      mine = Staged{cols[t], __double2loint(v), __double2hiint(v)};
+    }
+    const int cnt = e - base;
+    int u = 0;
+    if constexpr (GROUP >= 8) {
+      for (; u + 8 <= cnt; u += 8) consume8(mine, u);
+    }
+    for (; u + 4 <= cnt; u += 4) consume4(mine, u);
+    for (; u < cnt; ++u) consume(mine, u);
+  }
+
+  if (active) {
+    double *cr = C + (int64_t)row * k + col0;
+    if (is_split) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
+    } else if constexpr (BETA == 1) {
+      if constexpr (VEC == 2) {
+        double2 old = *reinterpret_cast<double2 *>(cr);
+        old.x += acc[0]; old.y += acc[1];
+        *reinterpret_cast<double2 *>(cr) = old;
+      } else {
+        cr[0] += acc[0];
+      }
+    } else {
+      if constexpr (VEC == 2) {
+        if (nt_mode) {
+          typedef double nt_double2 __attribute__((ext_vector_type(2)));
+          const nt_double2 outv = {acc[0], acc[1]};
+          __builtin_nontemporal_store(outv, reinterpret_cast<nt_double2 *>(cr));
+        } else {
+          *reinterpret_cast<double2 *>(cr) = double2{acc[0], acc[1]};
+        }
+      } else {
+        cr[0] = acc[0];
+      }
+    }
+  }
+}
+
+// The three schedulers, as for fp32 (grid-stride, block-grab queue,
+// wave-grab queue); see the comments on spmm_kernel / _q / _qw.
+template <int VEC, int GROUP, int BETA, bool GUARD>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_f64(
+    const int32_t *__restrict__ cols, const double *__restrict__ vals,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end, int64_t n_items,
+    const double *__restrict__ X0, const double *__restrict__ X1,
+    double *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
+    int nt_mode) {
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
+  const int lane_in_group = threadIdx.x % GROUP;
+  const int group_in_block = threadIdx.x / GROUP;
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
+  const bool active = !GUARD || (col0 < k);
+
+  int wg = blockIdx.x;
+  if (xcd_remap) {
+    const int nwg = gridDim.x;
+    const int q = nwg / 8, rm = nwg % 8;
+    const int xcd = blockIdx.x % 8, pos = blockIdx.x / 8;
+    wg = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + pos;
+  }
+
+  int64_t item = (int64_t)wg * GROUPS_PER_BLOCK + group_in_block;
+  const int64_t stride = (int64_t)gridDim.x * GROUPS_PER_BLOCK;
+
+  int32_t next_row = 0, next_b = 0, next_e = 0;
+  if (item < n_items) {
+    next_row = __builtin_nontemporal_load(&item_row[item]);
+    next_b = __builtin_nontemporal_load(&item_begin[item]);
+    next_e = __builtin_nontemporal_load(&item_end[item]);
+  }
+
+  for (; item < n_items; item += stride) {
+    const int32_t row_raw = next_row;
+    const int32_t b = next_b;
+    const int32_t e = next_e;
+    const int64_t nxt = item + stride;
+    if (nxt < n_items) {
+      next_row = __builtin_nontemporal_load(&item_row[nxt]);
+      next_b = __builtin_nontemporal_load(&item_begin[nxt]);
+      next_e = __builtin_nontemporal_load(&item_end[nxt]);
+    }
+    spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
+        cols, vals, row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group,
+        nt_mode);
+  }
+}
+
+template <int VEC, int GROUP, int BETA, bool GUARD>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q_f64(
+    const int32_t *__restrict__ cols, const double *__restrict__ vals,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
+    int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
+    int chunk_items,
+    const double *__restrict__ X0, const double *__restrict__ X1,
+    double *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
+  const int lane_in_group = threadIdx.x % GROUP;
+  const int group_in_block = threadIdx.x / GROUP;
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
+  const bool active = !GUARD || (col0 < k);
+  __shared__ int64_t s_base;
+
+  const unsigned q0 = arrow_xcc_id() & 7;
+  for (unsigned qi = 0; qi < 8; ++qi) {
+    const unsigned q = (q0 + qi) & 7;
+    const int64_t lo = qseg[q], hi = qseg[q + 1];
+    if (lo >= hi) continue;
+    for (;;) {
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        s_base = lo + (int64_t)atomicAdd(&qctr[q * 32], chunk_items);
+      }
+      __syncthreads();
+      const int64_t base = s_base;
+      if (base >= hi) break;
+      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
+      int64_t item = base + group_in_block;
+      int32_t next_row = 0, next_b = 0, next_e = 0;
+      if (item < end) {
+        next_row = __builtin_nontemporal_load(&item_row[item]);
+        next_b = __builtin_nontemporal_load(&item_begin[item]);
+        next_e = __builtin_nontemporal_load(&item_end[item]);
+      }
+      for (; item < end; item += GROUPS_PER_BLOCK) {
+        const int32_t row_raw = next_row;
+        const int32_t b = next_b;
+        const int32_t e = next_e;
+        const int64_t nxt = item + GROUPS_PER_BLOCK;
+        if (nxt < end) {
+          next_row = __builtin_nontemporal_load(&item_row[nxt]);
+          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
+          next_e = __builtin_nontemporal_load(&item_end[nxt]);
+        }
+        spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
+            cols, vals, row_raw, b, e, X0, X1, C, k, col0, active,
+            lane_in_group, nt_mode);
+      }
+    }
+  }
+}
+
+template <int VEC, int GROUP, int BETA, bool GUARD>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw_f64(
+    const int32_t *__restrict__ cols, const double *__restrict__ vals,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
+    int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
+    int chunk_items,                  // per-WAVE grab size (items)
+    const double *__restrict__ X0, const double *__restrict__ X1,
+    double *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
+  constexpr int GROUPS_PER_WAVE = 64 / GROUP;
+  const int lane = threadIdx.x & 63;
+  const int lane_in_group = threadIdx.x % GROUP;
+  const int group_in_wave = lane / GROUP;
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
+  const bool active = !GUARD || (col0 < k);
+
+  const unsigned q0 = arrow_xcc_id() & 7;
+  for (unsigned qi = 0; qi < 8; ++qi) {
+    const unsigned q = (q0 + qi) & 7;
+    const int64_t lo = qseg[q], hi = qseg[q + 1];
+    if (lo >= hi) continue;
+    for (;;) {
+      int grab = 0;
+      if (lane == 0) grab = atomicAdd(&qctr[q * 32], chunk_items);
+      grab = __shfl(grab, 0, 64);
+      const int64_t base = lo + grab;
+      if (base >= hi) break;
+      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
+      int64_t item = base + group_in_wave;
+      int32_t next_row = 0, next_b = 0, next_e = 0;
+      if (item < end) {
+        next_row = __builtin_nontemporal_load(&item_row[item]);
+        next_b = __builtin_nontemporal_load(&item_begin[item]);
+        next_e = __builtin_nontemporal_load(&item_end[item]);
+      }
+      for (; item < end; item += GROUPS_PER_WAVE) {
+        const int32_t row_raw = next_row;
+        const int32_t b = next_b;
+        const int32_t e = next_e;
+        const int64_t nxt = item + GROUPS_PER_WAVE;
+        if (nxt < end) {
+          next_row = __builtin_nontemporal_load(&item_row[nxt]);
+          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
+          next_e = __builtin_nontemporal_load(&item_end[nxt]);
+        }
+        spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
+            cols, vals, row_raw, b, e, X0, X1, C, k, col0, active,
+            lane_in_group, nt_mode);
+      }
+    }
+  }
+}
+
+__global__ void zero_rows_kernel_f64(double *__restrict__ C,
+                                     const int32_t *__restrict__ rows,
+                                     int64_t n_rows, int64_t k) {
+  const int64_t total = n_rows * k;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k, j = t % k;
+    C[(int64_t)rows[i] * k + j] = 0.0;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Row gather / scatter / scatter-add (permutation routing on-device).
 // ---------------------------------------------------------------------------
 
@@ -587,6 +938,51 @@ int launch_route(RouteOp op, float *dst, const float *src, const int64_t *idx,
   return 0;
 }
 
+// float64 adding routes: dst[dst_idx[i], :] += src[s, :] with s = src_idx[i]
+// (permute-add) or s = i when src_idx is null (scatter-add). The three pure
+// f64 copies reuse the fp32 kernels with each row viewed as 2k floats.
+template <int VEC>
+__global__ void route_add_rows_f64_kernel(double *__restrict__ dst,
+                                          const double *__restrict__ src,
+                                          const int64_t *__restrict__ dst_idx,
+                                          const int64_t *__restrict__ src_idx,
+                                          int64_t n, int64_t k_vec) {
+  const int64_t total = n * k_vec;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k_vec, j = t % k_vec;
+    const int64_t s = src_idx ? src_idx[i] : i;
+    if constexpr (VEC == 2) {
+      const double2 a = reinterpret_cast<const double2 *>(src)[s * k_vec + j];
+      double2 *d = reinterpret_cast<double2 *>(dst) + dst_idx[i] * k_vec + j;
+      double2 b = *d;
+      b.x += a.x; b.y += a.y;
+      *d = b;
+    } else {
+      dst[dst_idx[i] * k_vec + j] += src[s * k_vec + j];
+    }
+  }
+}
+
+int launch_route_add_f64(double *dst, const double *src, const int64_t *dst_idx,
+                         const int64_t *src_idx, int64_t n, int64_t k,
+                         hipStream_t stream) {
+  if (n == 0) return 0;
+  const bool vec2 = (k % 2 == 0);
+  const int64_t k_vec = vec2 ? k / 2 : k;
+  const int threads = 256;
+  int blocks = (int)std::min<int64_t>((n * k_vec + threads - 1) / threads, 16384);
+  if (vec2) {
+    hipLaunchKernelGGL(route_add_rows_f64_kernel<2>, dim3(blocks), dim3(threads),
+                       0, stream, dst, src, dst_idx, src_idx, n, k_vec);
+  } else {
+    hipLaunchKernelGGL(route_add_rows_f64_kernel<1>, dim3(blocks), dim3(threads),
+                       0, stream, dst, src, dst_idx, src_idx, n, k_vec);
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // SpMM dispatch over (VEC, GROUP, BETA, GUARD)
 // ---------------------------------------------------------------------------
@@ -685,13 +1081,29 @@ void pick_cfg(int64_t k, int *vec_out, int *group_out) {
   *group_out = group;
 }
 
+// float64: a lane holds VEC doubles — double2 (16 B, the bytes of the fp32
+// float4) when k is even. ARROW_SPMM_G64 / ARROW_K16_G8 are fp32 layout
+// experiments and do not apply.
+void pick_cfg_f64(int64_t k, int *vec_out, int *group_out) {
+  const int vec = (k % 2 == 0) ? 2 : 1;
+  const int64_t lanes_needed = (k + vec - 1) / vec;
+  int group = 1;
+  while (group < lanes_needed && group < 64) group <<= 1;
+  *vec_out = vec;
+  *group_out = group;
+}
+
 // queue_mode: the structure's arrow_csr_set_queue mode (-1 follows
 // ARROW_QUEUE); q_blocks_override: its arrow_csr_set_qblocks value (0 = none).
+// dtype 32 or 64 only selects the (vec, group) layout: the scheduler policy
+// and its thresholds are shared (a lane is 16 bytes in both precisions, so
+// GROUP-based thresholds carry over by row bytes; measured for fp32 only).
 SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
-                   int q_blocks_override) {
+                   int q_blocks_override, int dtype = 32) {
   const SpmmEnv &env = spmm_env();
   SpmmPlan p;
-  pick_cfg(k, &p.vec, &p.group);
+  if (dtype == 64) pick_cfg_f64(k, &p.vec, &p.group);
+  else             pick_cfg(k, &p.vec, &p.group);
   p.nt_mode = env.nt_mode;
   const int qd = queue_mode >= 0 ? (queue_mode ? 1 : 0) : env.queue_default;
   const bool useq = qd >= 0 ? (qd == 1)
@@ -786,6 +1198,80 @@ int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
   }
 }
 
+template <int VEC, int GROUP>
+int launch_spmm_vg_f64(const CsrBlock &blk, const SpmmPlan &plan,
+                       const double *X0, const double *X1, double *C,
+                       int64_t k, int beta, hipStream_t stream) {
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
+  const int nt_mode = plan.nt_mode;
+  const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
+  const bool qwave = plan.scheduler == SCHED_QUEUE_WAVE;
+  if (useq && !(blk.qseg && blk.qctr)) {
+    set_error("arrow_spmm_f64: structure has no queue segments");
+    return -1;
+  }
+  int blocks = (int)std::min<int64_t>(
+      (blk.n_items + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK, plan.grid_cap);
+  if (blocks < 1) blocks = 1;
+  const int64_t span = (int64_t)GROUP * VEC;
+  for (int64_t col_off = 0; col_off < k; col_off += span) {
+    const bool guard = (col_off + span > k);
+    auto run = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                         blk.cols64, blk.vals64, blk.item_row, blk.item_begin,
+                         blk.item_end, blk.n_items, X0, X1, C, k, col_off,
+                         blk.xcd_remap, nt_mode);
+    };
+    auto runq = [&](auto kern, int chunk) {
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                         blk.cols64, blk.vals64, blk.item_row, blk.item_begin,
+                         blk.item_end, blk.qseg, blk.qctr, chunk,
+                         X0, X1, C, k, col_off, nt_mode);
+    };
+    if (useq) {
+      HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
+      if (qwave) {
+        if (beta == 0) {
+          if (guard) runq(spmm_kernel_qw_f64<VEC, GROUP, 0, true>, plan.chunk_items);
+          else       runq(spmm_kernel_qw_f64<VEC, GROUP, 0, false>, plan.chunk_items);
+        } else {
+          if (guard) runq(spmm_kernel_qw_f64<VEC, GROUP, 1, true>, plan.chunk_items);
+          else       runq(spmm_kernel_qw_f64<VEC, GROUP, 1, false>, plan.chunk_items);
+        }
+      } else if (beta == 0) {
+        if (guard) runq(spmm_kernel_q_f64<VEC, GROUP, 0, true>, plan.chunk_items);
+        else       runq(spmm_kernel_q_f64<VEC, GROUP, 0, false>, plan.chunk_items);
+      } else {
+        if (guard) runq(spmm_kernel_q_f64<VEC, GROUP, 1, true>, plan.chunk_items);
+        else       runq(spmm_kernel_q_f64<VEC, GROUP, 1, false>, plan.chunk_items);
+      }
+    } else if (beta == 0) {
+      if (guard) run(spmm_kernel_f64<VEC, GROUP, 0, true>);
+      else       run(spmm_kernel_f64<VEC, GROUP, 0, false>);
+    } else {
+      if (guard) run(spmm_kernel_f64<VEC, GROUP, 1, true>);
+      else       run(spmm_kernel_f64<VEC, GROUP, 1, false>);
+    }
+    HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+template <int VEC>
+int launch_spmm_v_f64(const CsrBlock &blk, const SpmmPlan &plan,
+                      const double *X0, const double *X1, double *C, int64_t k,
+                      int beta, hipStream_t stream) {
+  switch (plan.group) {
+    case 1:  return launch_spmm_vg_f64<VEC, 1>(blk, plan, X0, X1, C, k, beta, stream);
+    case 2:  return launch_spmm_vg_f64<VEC, 2>(blk, plan, X0, X1, C, k, beta, stream);
+    case 4:  return launch_spmm_vg_f64<VEC, 4>(blk, plan, X0, X1, C, k, beta, stream);
+    case 8:  return launch_spmm_vg_f64<VEC, 8>(blk, plan, X0, X1, C, k, beta, stream);
+    case 16: return launch_spmm_vg_f64<VEC, 16>(blk, plan, X0, X1, C, k, beta, stream);
+    case 32: return launch_spmm_vg_f64<VEC, 32>(blk, plan, X0, X1, C, k, beta, stream);
+    default: return launch_spmm_vg_f64<VEC, 64>(blk, plan, X0, X1, C, k, beta, stream);
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -816,8 +1302,8 @@ int arrow_synchronize(void) {
 
 static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
                                const int64_t *indptr, const int32_t *indices,
-                               const float *data, const int64_t *row_ids,
-                               int flags = 0) {
+                               const void *data, const int64_t *row_ids,
+                               int flags = 0, int dtype = 32) {
   if (rows < 0 || cols < 0 || nnz < 0 || (rows > 0 && !indptr)) {
     set_error("arrow_csr_create: bad arguments");
     return -1;
@@ -830,6 +1316,7 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
   blk.rows = rows;
   blk.cols = cols;
   blk.nnz = nnz;
+  blk.dtype = dtype;
 
   // Build work items on the host: every row gets at least one item; rows
   // with > SEG_NNZ nonzeros are split and marked atomic (bit 31).
@@ -942,12 +1429,17 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
     }
   }
 
-  // pack (col, val) into 8-byte pairs for the staged kernel loads
-  std::vector<int2> pairs((size_t)nnz);
-  for (int64_t t = 0; t < nnz; ++t) {
-    pairs[(size_t)t].x = indices[t];
-    float v = data[t];
-    pairs[(size_t)t].y = *reinterpret_cast<const int32_t *>(&v);
+  // fp32: pack (col, val) into 8-byte pairs for the staged kernel loads.
+  // float64: the caller's arrays are the resident layout as they are
+  // (split int32 cols[] + double vals[])
+  std::vector<int2> pairs(dtype == 32 ? (size_t)nnz : 0);
+  if (dtype == 32) {
+    const float *data32 = static_cast<const float *>(data);
+    for (int64_t t = 0; t < nnz; ++t) {
+      pairs[(size_t)t].x = indices[t];
+      float v = data32[t];
+      pairs[(size_t)t].y = *reinterpret_cast<const int32_t *>(&v);
+    }
   }
 
   auto upload = [&](void **dst, const void *src, size_t bytes) -> int {
@@ -957,6 +1449,9 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
     return 0;
   };
   if (upload((void **)&blk.pairs, pairs.data(), pairs.size() * sizeof(int2)) ||
+      (dtype == 64 &&
+       (upload((void **)&blk.cols64, indices, (size_t)nnz * sizeof(int32_t)) ||
+        upload((void **)&blk.vals64, data, (size_t)nnz * sizeof(double)))) ||
       upload((void **)&blk.item_row, item_row.data(), item_row.size() * 4) ||
       upload((void **)&blk.item_begin, item_begin.data(), item_begin.size() * 4) ||
       upload((void **)&blk.item_end, item_end.data(), item_end.size() * 4) ||
@@ -997,13 +1492,31 @@ int arrow_csr_destroy(int64_t handle) {
     return -1;
   }
   CsrBlock &b = it->second;
-  for (void *p : {(void *)b.pairs, (void *)b.item_row,
+  for (void *p : {(void *)b.pairs, (void *)b.cols64, (void *)b.vals64,
+                  (void *)b.item_row,
                   (void *)b.item_begin, (void *)b.item_end,
                   (void *)b.split_rows, (void *)b.qseg, (void *)b.qctr}) {
     if (p) (void)hipFree(p);
   }
   g_blocks.erase(it);
   return 0;
+}
+
+int64_t arrow_csr_create_f64(int64_t rows, int64_t cols, int64_t nnz,
+                             const int64_t *indptr, const int32_t *indices,
+                             const double *data, const int64_t *row_ids,
+                             int flags) {
+  return csr_create_impl(rows, cols, nnz, indptr, indices, data, row_ids,
+                         flags, 64);
+}
+
+int arrow_csr_dtype(int64_t handle) {
+  auto it = g_blocks.find(handle);
+  if (it == g_blocks.end()) {
+    set_error("arrow_csr_dtype: bad handle");
+    return -1;
+  }
+  return it->second.dtype;
 }
 
 int64_t arrow_csr_nnz(int64_t handle) {
@@ -1054,6 +1567,12 @@ int arrow_spmm_dual(int64_t handle, const float *X0_dev, const float *X1_dev,
     return -1;
   }
   const CsrBlock &blk = it->second;
+  if (blk.dtype != 32) {
+    set_error("arrow_spmm: handle holds a float64 structure "
+              "(arrow_csr_create_f64) but was passed to the float32 entry "
+              "point; use arrow_spmm_f64 / arrow_spmm_dual_f64");
+    return -2;
+  }
   hipStream_t stream = (hipStream_t)stream_v;
 
   // beta=0: split rows are accumulated with atomics, so pre-zero them.
@@ -1090,6 +1609,104 @@ int arrow_spmm_plan(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
 int arrow_spmm(int64_t handle, const float *X_dev, float *C_dev, int64_t k,
                int beta, void *stream_v) {
   return arrow_spmm_dual(handle, X_dev, X_dev, C_dev, k, beta, stream_v);
+}
+
+int arrow_spmm_dual_f64(int64_t handle, const double *X0_dev,
+                        const double *X1_dev, double *C_dev, int64_t k,
+                        int beta, void *stream_v) {
+  auto it = g_blocks.find(handle);
+  if (it == g_blocks.end()) {
+    set_error("arrow_spmm_f64: bad handle");
+    return -1;
+  }
+  if (k <= 0 || !X0_dev || !X1_dev || !C_dev) {
+    set_error("arrow_spmm_f64: bad arguments");
+    return -1;
+  }
+  const CsrBlock &blk = it->second;
+  if (blk.dtype != 64) {
+    set_error("arrow_spmm_f64: handle holds a float32 structure "
+              "(arrow_csr_create) but was passed to the float64 entry "
+              "point; use arrow_spmm / arrow_spmm_dual");
+    return -2;
+  }
+  hipStream_t stream = (hipStream_t)stream_v;
+
+  // beta=0: split rows are accumulated with atomics, so pre-zero them.
+  if (beta == 0 && blk.n_split_rows > 0) {
+    const int64_t total = blk.n_split_rows * k;
+    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(zero_rows_kernel_f64, dim3(blocks), dim3(256), 0,
+                       stream, C_dev, blk.split_rows, blk.n_split_rows, k);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  const SpmmPlan plan = spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, 64);
+  if (plan.vec == 2)
+    return launch_spmm_v_f64<2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
+  return launch_spmm_v_f64<1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
+}
+
+int arrow_spmm_f64(int64_t handle, const double *X_dev, double *C_dev,
+                   int64_t k, int beta, void *stream_v) {
+  return arrow_spmm_dual_f64(handle, X_dev, X_dev, C_dev, k, beta, stream_v);
+}
+
+int arrow_spmm_plan_f64(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                        int n_out) {
+  if (k <= 0 || nnz < 0 || !out || n_out < 0) {
+    set_error("arrow_spmm_plan_f64: bad arguments");
+    return -1;
+  }
+  const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0, 64);
+  const int32_t fields[ARROW_PLAN_FIELDS] = {
+      p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
+      p.n_launches};
+  for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
+  return ARROW_PLAN_FIELDS;
+}
+
+// float64 routing: the pure copies move each row as 2k floats through the
+// fp32 kernels (bit-exact, and float4 = two doubles when k is even); the
+// two adding forms do double arithmetic.
+int arrow_permute_rows_f64(double *dst, const double *src,
+                           const int64_t *dst_idx, const int64_t *src_idx,
+                           int64_t n, int64_t k, void *stream) {
+  return launch_permute(0, reinterpret_cast<float *>(dst),
+                        reinterpret_cast<const float *>(src), dst_idx, src_idx,
+                        n, 2 * k, (hipStream_t)stream);
+}
+
+int arrow_permute_add_rows_f64(double *dst, const double *src,
+                               const int64_t *dst_idx, const int64_t *src_idx,
+                               int64_t n, int64_t k, void *stream) {
+  if (n > 0 && !src_idx) {
+    set_error("arrow_permute_add_rows_f64: src_idx is NULL");
+    return -1;
+  }
+  return launch_route_add_f64(dst, src, dst_idx, src_idx, n, k,
+                              (hipStream_t)stream);
+}
+
+int arrow_gather_rows_f64(const double *src, double *dst, const int64_t *idx,
+                          int64_t n, int64_t k, void *stream) {
+  return launch_route(RouteOp::Gather, reinterpret_cast<float *>(dst),
+                      reinterpret_cast<const float *>(src), idx, n, 2 * k,
+                      (hipStream_t)stream);
+}
+
+int arrow_scatter_rows_f64(double *dst, const double *src, const int64_t *idx,
+                           int64_t n, int64_t k, void *stream) {
+  return launch_route(RouteOp::Scatter, reinterpret_cast<float *>(dst),
+                      reinterpret_cast<const float *>(src), idx, n, 2 * k,
+                      (hipStream_t)stream);
+}
+
+int arrow_scatter_add_rows_f64(double *dst, const double *src,
+                               const int64_t *idx, int64_t n, int64_t k,
+                               void *stream) {
+  return launch_route_add_f64(dst, src, idx, nullptr, n, k,
+                              (hipStream_t)stream);
 }
 
 int arrow_permute_rows_f32(float *dst, const float *src, const int64_t *dst_idx,

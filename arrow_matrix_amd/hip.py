@@ -84,6 +84,27 @@ def _load():
                        ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                        ctypes.c_void_p]
         fn.restype = ctypes.c_int
+    # float64 entry points (ABI 1003)
+    lib.arrow_csr_create_f64.restype = ctypes.c_int64
+    lib.arrow_csr_create_f64.argtypes = [
+        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
+        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
+        ctypes.c_int]
+    lib.arrow_csr_dtype.argtypes = [ctypes.c_int64]
+    lib.arrow_csr_dtype.restype = ctypes.c_int
+    lib.arrow_spmm_f64.argtypes = lib.arrow_spmm.argtypes
+    lib.arrow_spmm_f64.restype = ctypes.c_int
+    lib.arrow_spmm_dual_f64.argtypes = lib.arrow_spmm_dual.argtypes
+    lib.arrow_spmm_dual_f64.restype = ctypes.c_int
+    lib.arrow_spmm_plan_f64.argtypes = lib.arrow_spmm_plan.argtypes
+    lib.arrow_spmm_plan_f64.restype = ctypes.c_int
+    for name in ('arrow_gather_rows', 'arrow_scatter_rows',
+                 'arrow_scatter_add_rows', 'arrow_permute_rows',
+                 'arrow_permute_add_rows'):
+        fn = getattr(lib, name + '_f64')
+        fn.argtypes = getattr(lib, name + '_f32').argtypes
+        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -98,18 +119,37 @@ def _check(rc, what: str):
     return rc
 
 
+def _suffix(dtype) -> str:
+    """'f32' or 'f64' for a supported dtype; TypeError for any other."""
+    try:
+        dt = np.dtype(dtype)
+    except TypeError:
+        dt = None
+    if dt == np.float32:
+        return 'f32'
+    if dt == np.float64:
+        return 'f64'
+    raise TypeError(f"the HIP kernels compute in float32 or float64, "
+                    f"not {dtype!r}")
+
+
 class CsrBlockGPU:
     """A CSR block resident in HBM (uploaded ONCE — unlike the reference,
     which re-uploads A every iteration, arrow_slim_mpi.py:184-232)."""
 
-    def __init__(self, csr=None, arrays=None, row_ids=None, col_items=False):
+    def __init__(self, csr=None, arrays=None, row_ids=None, col_items=False,
+                 dtype=np.float32):
         """csr: scipy CSR, or arrays=(shape, indptr, indices, data) for raw
         uploads (the fused layouts use negative column indices, which scipy
         would reject). row_ids: optional explicit output-row id per
         structure row (reordered layouts). col_items: work-item ordering
         mode (hub structures; see arrow_csr_create_opts flags): 0/False
         row order, 1/True global column sort, 2 column sort WITHIN each
-        XCD queue segment (two-level)."""
+        XCD queue segment (two-level). dtype: float32 or float64 — the
+        precision of the resident values, fixed here; spmm / spmm_dual
+        then take device pointers of that precision."""
+        self._f64 = _suffix(dtype) == 'f64'
+        self.dtype = np.dtype(dtype)
         lib = _load()
         if arrays is not None:
             (rows, cols), indptr, indices, data = arrays
@@ -119,10 +159,21 @@ class CsrBlockGPU:
             indptr, indices, data = csr.indptr, csr.indices, csr.data
         indptr = np.ascontiguousarray(indptr, dtype=np.int64)
         indices = np.ascontiguousarray(indices, dtype=np.int32)
-        data = np.ascontiguousarray(data, dtype=np.float32)
+        data = np.ascontiguousarray(data, dtype=self.dtype)
         self.shape = (rows, cols)
         self.nnz = int(indices.size)
-        if col_items:
+        if self._f64:
+            rid = (np.ascontiguousarray(row_ids, dtype=np.int64)
+                   if row_ids is not None else None)
+            self._handle = _check(lib.arrow_csr_create_f64(
+                rows, cols, self.nnz,
+                indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                data.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                (rid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+                 if rid is not None else None), int(col_items)),
+                "arrow_csr_create_f64")
+        elif col_items:
             rid = (np.ascontiguousarray(row_ids, dtype=np.int64)
                    if row_ids is not None else None)
             self._handle = _check(lib.arrow_csr_create_opts(
@@ -152,8 +203,13 @@ class CsrBlockGPU:
 
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0):
         """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr())."""
-        _check(_load().arrow_spmm(self._handle, X_ptr, C_ptr, k, beta, stream),
-               "arrow_spmm")
+        lib = _load()
+        if self._f64:
+            _check(lib.arrow_spmm_f64(self._handle, X_ptr, C_ptr, k, beta,
+                                      stream), "arrow_spmm_f64")
+        else:
+            _check(lib.arrow_spmm(self._handle, X_ptr, C_ptr, k, beta, stream),
+                   "arrow_spmm")
 
     def set_xcd_remap(self, enable: bool):
         _check(_load().arrow_csr_set_xcd_remap(self._handle, 1 if enable else 0),
@@ -173,7 +229,13 @@ class CsrBlockGPU:
                   beta: int, stream: int = 0):
         """Fused dual-operand SpMM: negative column indices (encoded at
         upload as -(idx+1)) read X1 (see include/arrow_spmm.h)."""
-        _check(_load().arrow_spmm_dual(self._handle, X0_ptr, X1_ptr, C_ptr,
+        lib = _load()
+        if self._f64:
+            _check(lib.arrow_spmm_dual_f64(self._handle, X0_ptr, X1_ptr, C_ptr,
+                                           k, beta, stream),
+                   "arrow_spmm_dual_f64")
+        else:
+            _check(lib.arrow_spmm_dual(self._handle, X0_ptr, X1_ptr, C_ptr,
                                        k, beta, stream), "arrow_spmm_dual")
 
     def __del__(self):
@@ -192,31 +254,39 @@ def synchronize():
     _check(_load().arrow_synchronize(), "arrow_synchronize")
 
 
-def gather_rows(src_ptr: int, dst_ptr: int, idx_ptr: int, n: int, k: int, stream: int = 0):
-    _check(_load().arrow_gather_rows_f32(src_ptr, dst_ptr, idx_ptr, n, k, stream),
-           "arrow_gather_rows_f32")
+def _route(name: str, dtype):
+    name = f'arrow_{name}_{_suffix(dtype)}'
+    return getattr(_load(), name), name
 
 
-def scatter_rows(dst_ptr: int, src_ptr: int, idx_ptr: int, n: int, k: int, stream: int = 0):
-    _check(_load().arrow_scatter_rows_f32(dst_ptr, src_ptr, idx_ptr, n, k, stream),
-           "arrow_scatter_rows_f32")
+def gather_rows(src_ptr: int, dst_ptr: int, idx_ptr: int, n: int, k: int,
+                stream: int = 0, dtype=np.float32):
+    fn, name = _route('gather_rows', dtype)
+    _check(fn(src_ptr, dst_ptr, idx_ptr, n, k, stream), name)
 
 
-def scatter_add_rows(dst_ptr: int, src_ptr: int, idx_ptr: int, n: int, k: int, stream: int = 0):
-    _check(_load().arrow_scatter_add_rows_f32(dst_ptr, src_ptr, idx_ptr, n, k, stream),
-           "arrow_scatter_add_rows_f32")
+def scatter_rows(dst_ptr: int, src_ptr: int, idx_ptr: int, n: int, k: int,
+                 stream: int = 0, dtype=np.float32):
+    fn, name = _route('scatter_rows', dtype)
+    _check(fn(dst_ptr, src_ptr, idx_ptr, n, k, stream), name)
 
 
-def permute_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream=0):
-    _check(_load().arrow_permute_rows_f32(dst_ptr, src_ptr, dst_idx_ptr,
-                                          src_idx_ptr, n, k, stream),
-           "arrow_permute_rows_f32")
+def scatter_add_rows(dst_ptr: int, src_ptr: int, idx_ptr: int, n: int, k: int,
+                     stream: int = 0, dtype=np.float32):
+    fn, name = _route('scatter_add_rows', dtype)
+    _check(fn(dst_ptr, src_ptr, idx_ptr, n, k, stream), name)
 
 
-def permute_add_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream=0):
-    _check(_load().arrow_permute_add_rows_f32(dst_ptr, src_ptr, dst_idx_ptr,
-                                              src_idx_ptr, n, k, stream),
-           "arrow_permute_add_rows_f32")
+def permute_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream=0,
+                 dtype=np.float32):
+    fn, name = _route('permute_rows', dtype)
+    _check(fn(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream), name)
+
+
+def permute_add_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k,
+                     stream=0, dtype=np.float32):
+    fn, name = _route('permute_add_rows', dtype)
+    _check(fn(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream), name)
 
 
 PLAN_FIELDS = ('vec', 'group', 'scheduler', 'nt_mode', 'chunk_items',
@@ -224,13 +294,17 @@ PLAN_FIELDS = ('vec', 'group', 'scheduler', 'nt_mode', 'chunk_items',
 SCHED_GRID_STRIDE, SCHED_QUEUE_BLOCK, SCHED_QUEUE_WAVE = 0, 1, 2
 
 
-def spmm_plan(k: int, nnz: int, queue_mode: int = -1) -> dict:
-    """The launch plan arrow_spmm takes for a structure of `nnz` nonzeros at
-    width k (arrow_spmm_plan; needs no device). The ARROW_* kernel-tuning
+def spmm_plan(k: int, nnz: int, queue_mode: int = -1,
+              dtype=np.float32) -> dict:
+    """The launch plan arrow_spmm (or, for dtype float64, arrow_spmm_f64)
+    takes for a structure of `nnz` nonzeros at width k (arrow_spmm_plan /
+    arrow_spmm_plan_f64; needs no device). The ARROW_* kernel-tuning
     variables are read once per process, on first use."""
+    name = ('arrow_spmm_plan_f64' if _suffix(dtype) == 'f64'
+            else 'arrow_spmm_plan')
     out = (ctypes.c_int32 * len(PLAN_FIELDS))()
-    n = _check(_load().arrow_spmm_plan(int(k), int(nnz), int(queue_mode), out,
-                                       len(PLAN_FIELDS)), "arrow_spmm_plan")
+    n = _check(getattr(_load(), name)(int(k), int(nnz), int(queue_mode), out,
+                                      len(PLAN_FIELDS)), name)
     if n != len(PLAN_FIELDS):
         raise ArrowSpmmError(f"arrow_spmm_plan: library has {n} plan fields, "
                              f"binding expects {len(PLAN_FIELDS)}")

@@ -32,10 +32,6 @@ def benchmark_spmm(matrix_slice_file: Optional[str], k: int, iterations: int,
         raise NotImplementedError(
             "GPU column tiling (spmm_petsc.py:323-395) is unnecessary with "
             "288 GB HBM3E per GPU and is not reproduced (DESIGN.md §next)")
-    if np.dtype(dtype) != np.float32 and device != 'cpu':
-        raise NotImplementedError(
-            "the HIP kernels compute in fp32 (the reference benchmark "
-            "default, arrow_bench.py:21); float64 runs with --device cpu")
     rng = rng if rng is not None else np.random.default_rng(42)
     comm = default_comm()
     name = "PETSc_v0.1_AMD"
@@ -62,7 +58,7 @@ def benchmark_spmm(matrix_slice_file: Optional[str], k: int, iterations: int,
         return None
 
     ms = MatrixSlice.initialize(comm, sparse.csr_matrix(A_i))
-    engine = SpmmPETSc(comm, ms, device=device)
+    engine = SpmmPETSc(comm, ms, device=device, dtype=dtype)
 
     Y = None
     for i in range(iterations):

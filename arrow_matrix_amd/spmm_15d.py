@@ -36,7 +36,7 @@ except Exception:  # pragma: no cover
 class Spmm15D:
 
     def __init__(self, comm: Optional[Comm], A: sparse.csr_matrix, X_cols: int,
-                 c: int = 1, device: str = 'cpu'):
+                 c: int = 1, device: str = 'cpu', dtype=np.float32):
         """:param A: the FULL matrix (every rank slices its own panels).
         :param c: replication factor; world size must equal (P/c)·c with
         P/c divisible by c (reference :35-41)."""
@@ -55,7 +55,7 @@ class Spmm15D:
         rank = self.comm.rank
         self.x, self.y = rank // c, rank % c  # row-major cartesian coords
 
-        self.backend = make_backend(device)
+        self.backend = make_backend(device, dtype)
         A = sparse.csr_matrix(A)
         NI, NK = A.shape
         self.NK = NK

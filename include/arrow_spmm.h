@@ -149,6 +149,75 @@ int arrow_permute_add_rows_f32(float *dst_dev, const float *src_dev,
                                const int64_t *dst_idx_dev, const int64_t *src_idx_dev,
                                int64_t n, int64_t k, void *stream);
 
+/* ---------------------------------------------------------------------
+ * float64 (ABI 1003). The reference's precision knob — `datatype=` on
+ * bench_spmm / load_decomposition_new (arrow_bench.py:21,
+ * arrow_dec_mpi.py:629), `dtype=` on zero_rhs (arrow_slim_mpi.py:354),
+ * `-t float64` on the PETSc and 1.5D CLIs — runs on the GPU there through
+ * cupy's float64 CSRMM; these exports replace that.
+ *
+ * A structure's precision is fixed when it is created. Raw device pointers
+ * carry no type, so the handle's tag is the only guard: a handle passed to
+ * the other precision's SpMM entry point returns a negative code, sets an
+ * arrow_last_error() message naming both precisions, and launches nothing.
+ * ------------------------------------------------------------------- */
+
+/* Upload a CSR block with float64 values (replaces sp2cp.py:6-16 for a
+ * float64 csr_matrix). Same arguments as arrow_csr_create_opts; row_ids may
+ * be NULL. Resident layout: split int32 cols[] + double vals[], 12 B/nnz. */
+int64_t arrow_csr_create_f64(int64_t rows, int64_t cols, int64_t nnz,
+                             const int64_t *indptr, const int32_t *indices,
+                             const double *data, const int64_t *row_ids,
+                             int flags);
+/* Precision of a resident block: 32 or 64 (negative on a bad handle). */
+int arrow_csr_dtype(int64_t handle);
+
+/* C (+)= A @ X in float64 (replaces the cupy `A @ X` CSRMM,
+ * arrow_slim_mpi.py:190,211,231, at dtype float64). X: (cols, k) float64
+ * row-major device; C: (rows, k). X and C rows must be 16-byte aligned when
+ * k is even (any torch allocation is). Accumulates in double with fma;
+ * split hub rows add with the hardware float64 global atomic. */
+int arrow_spmm_f64(int64_t handle, const double *X_dev, double *C_dev,
+                   int64_t k, int beta, void *stream);
+/* Dual-operand form, as arrow_spmm_dual (arrow_slim_mpi.py:121-144). */
+int arrow_spmm_dual_f64(int64_t handle, const double *X0_dev,
+                        const double *X1_dev, double *C_dev, int64_t k,
+                        int beta, void *stream);
+
+/* Launch-plan query for the float64 entry points: the same seven fields as
+ * arrow_spmm_plan, from the same policy and the same once-per-process
+ * environment. ARROW_PLAN_VEC counts doubles per lane: 2 when k is even
+ * (16 bytes, as the fp32 float4), else 1; GROUP = the power of two >=
+ * ceil(k / vec), capped at 64. The queue policy (GROUP >= 4 and nnz >=
+ * ARROW_Q_MIN_NNZ), wave grabs at GROUP < 8 and the chunk and grid
+ * variables apply unchanged: a lane is 16 bytes in both precisions, so the
+ * GROUP-based thresholds carry over by row bytes — but they were MEASURED
+ * FOR FP32 ONLY. ARROW_SPMM_G64 and ARROW_K16_G8 are fp32 layout
+ * experiments and are ignored by the float64 plan. */
+int arrow_spmm_plan_f64(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                        int n_out);
+
+/* float64 routing (replace the host fancy-indexing of arrow_dec_mpi.py at
+ * dtype float64): gather :421,526; scatter :544; scatter-add :437; the
+ * fused rank-local permute :526+544 and permute-add :421+437. */
+int arrow_gather_rows_f64(const double *src_dev, double *dst_dev,
+                          const int64_t *idx_dev, int64_t n, int64_t k,
+                          void *stream);
+int arrow_scatter_rows_f64(double *dst_dev, const double *src_dev,
+                           const int64_t *idx_dev, int64_t n, int64_t k,
+                           void *stream);
+int arrow_scatter_add_rows_f64(double *dst_dev, const double *src_dev,
+                               const int64_t *idx_dev, int64_t n, int64_t k,
+                               void *stream);
+int arrow_permute_rows_f64(double *dst_dev, const double *src_dev,
+                           const int64_t *dst_idx_dev,
+                           const int64_t *src_idx_dev, int64_t n, int64_t k,
+                           void *stream);
+int arrow_permute_add_rows_f64(double *dst_dev, const double *src_dev,
+                               const int64_t *dst_idx_dev,
+                               const int64_t *src_idx_dev, int64_t n,
+                               int64_t k, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,8 +35,7 @@ def main():
     parser.add_argument('-z', '--iterations', type=int, default=10)
     args = vars(parser.parse_args())
 
-    if args['type'] != 'float32':
-        raise NotImplementedError("fp32 only (DESIGN.md §next)")
+    dtype = np.float32 if args['type'] == 'float32' else np.float64
 
     comm = default_comm()
     rng = np.random.default_rng(args['seed'])
@@ -48,22 +47,22 @@ def main():
 
     from scipy import sparse
     if args['dataset'] == 'file':
-        A = sparse.load_npz(args['file']).tocsr().astype(np.float32)
+        A = sparse.load_npz(args['file']).tocsr().astype(dtype)
     else:
         A = utils.generate_sparse_matrix(args['vertices'], args['vertices'],
-                                         args['edges'], np.float32, rng)
+                                         args['edges'], dtype, rng)
 
     wb_logging.wandb_init(comm, args['file'], args['columns'],
                           args['iterations'], args['device'], "15D_v0.1_AMD", 0,
                           os.environ.get('WANDB_API_KEY'))
 
     eng = Spmm15D(comm, A, args['columns'], c=args['replication'],
-                  device=args['device'])
+                  device=args['device'], dtype=dtype)
     x0 = eng.x * eng.lNKb
     X_full = None
     for i in range(args['iterations']):
         X_full = 2 * rng.random((A.shape[1], args['columns']),
-                                dtype=np.float32) - 1
+                                dtype=dtype) - 1
         X_local = X_full[x0:min(A.shape[1], x0 + eng.lNKb)]
         wb_logging.set_iteration_data({"iteration": i})
         tic = time.perf_counter()

@@ -1,0 +1,181 @@
+"""float64 through the engine on one GPU: load_decomposition_new(datatype=
+float64) -> initialize(device='gpu', dtype=float64) -> zero_rhs(dtype=
+float64), against synth.recompose(decomp).astype(float64) @ X.
+
+The gate is test_engine_cpu_float64's: rtol = 1e-12 and atol = 1e-12 scaled
+by max|golden|. The engine paths that an environment variable selects
+(two-launch layout, sequential / full / row fold, allreduce_x0) and the
+banded mode each run in a child process (tests/engine_f64_driver.py) and
+must match the default path on the same matrix to the same gate; the banded
+decomposition is a matrix of its own, so it is held to its golden.
+"""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from tests import engine_f64_driver as drv
+from tests.spmm_cases import SEG_NNZ
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER = os.path.join(REPO, 'tests', 'engine_f64_driver.py')
+TOL = 1e-12
+CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
+
+_gpu_stopped = None
+
+
+def _need_gpu():
+    """Every test starts here: after a child has aborted, faulted or hit its
+    limit, no later test of this file starts GPU work, in-process or not."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    if _gpu_stopped:
+        pytest.fail(f"not started: {_gpu_stopped}", pytrace=False)
+
+
+def _close(C, G):
+    scale = float(np.abs(G).max())
+    np.testing.assert_allclose(C, G, rtol=TOL, atol=TOL * scale)
+
+
+@pytest.mark.parametrize("n_blocks,width,k,seed,extra", [
+    ([3], 64, 32, 0, {}),
+    ([4, 2], 50, 8, 1, {}),
+    ([4, 3, 2], 32, 16, 2, {}),
+    ([3], 48, 300, 3, {}),
+    ([2], 40, 7, 4, {}),
+    # two hub rows of 8000 draws over 2560 columns: about 2450 distinct
+    # nonzeros each, above the 2048 of one work item, so the fused structure
+    # has split rows and their float64 atomics run (asserted below)
+    ([5], 512, 8, 5, dict(hub_rows=2, hub_deg=8000)),
+])
+def test_engine_gpu_f64_matches_golden(n_blocks, width, k, seed, extra):
+    _need_gpu()
+    if extra.get('hub_rows'):
+        B0 = drv.make_decomposition(n_blocks, width, seed, **extra)[0][0]
+        assert np.diff(B0.indptr).max() > SEG_NNZ
+    results, goldens, arrow = drv.run_f64(n_blocks, width, k, seed, **extra)
+    assert arrow.B.backend.np_dtype == np.float64
+    assert arrow.B.result_tile().dtype == torch.float64
+    _close(results[0], goldens[0])
+
+
+def test_engine_gpu_f64_iterated():
+    _need_gpu()
+    results, goldens, _ = drv.run_f64([3, 2], 64, 16, 7, iters=3)
+    assert len(results) == 3
+    for C, G in zip(results, goldens):
+        _close(C, G)
+
+
+_default_cache = {}
+
+
+def _default_results(kwargs):
+    key = repr(sorted(kwargs.items()))
+    if key not in _default_cache:
+        for var in drv.ENGINE_VARS:
+            assert var not in os.environ, var
+        _default_cache[key] = drv.run_f64(**kwargs)[0]
+    return _default_cache[key]
+
+
+@pytest.mark.parametrize('mode', list(drv.MODES))
+def test_engine_gpu_f64_paths(mode):
+    """Each environment-selected path, in a child that starts with it."""
+    global _gpu_stopped
+    _need_gpu()
+    variables, kwargs = drv.MODES[mode]
+    env = {k: v for k, v in os.environ.items() if k not in drv.ENGINE_VARS}
+    env.update(variables)
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, 'out.npy')
+        try:
+            p = subprocess.run([sys.executable, DRIVER, mode, out], cwd=REPO,
+                               env=env, capture_output=True, text=True,
+                               timeout=CHILD_LIMIT_S)
+        except subprocess.TimeoutExpired:
+            _gpu_stopped = f"engine child '{mode}' hit its {CHILD_LIMIT_S}s limit"
+            pytest.fail(_gpu_stopped, pytrace=False)
+        if p.returncode < 0 or p.returncode in (134, 139, 124, 137):
+            _gpu_stopped = f"engine child '{mode}' ended with status {p.returncode}"
+            pytest.fail(_gpu_stopped + "\n" + p.stderr[-2000:], pytrace=False)
+        assert p.returncode == 0, p.stderr[-2000:]
+        results, goldens = np.load(out)
+    assert results.dtype == np.float64 and len(results) == kwargs['iters']
+    for C, G in zip(results, goldens):
+        _close(C, G)
+    if mode in drv.DEFAULT_OF:
+        for C, D in zip(results, _default_results(drv.DEFAULT_OF[mode])):
+            _close(C, D)
+
+
+def test_zero_rhs_dtype_is_fixed_at_construction():
+    _need_gpu()
+    from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
+    from arrow_matrix_amd.arrow_mpi import ArrowMPI
+    e64 = ArrowSlimMPI(None, tiles_per_side=2, device='gpu', dtype=np.float64)
+    with pytest.raises(TypeError, match='construct'):
+        e64.zero_rhs(8, 4, dtype=np.float32)
+    e64.zero_rhs(8, 4, dtype=np.float64)
+    assert e64.C_i.dtype == torch.float64 and e64.X_0.dtype == torch.float64
+    e32 = ArrowSlimMPI(None, tiles_per_side=2, device='gpu')
+    with pytest.raises(TypeError, match='construct'):
+        e32.zero_rhs(8, 4, dtype=np.float64)
+    e32.zero_rhs(8, 4)
+    assert e32.C_i.dtype == torch.float32
+    b64 = ArrowMPI(None, tiles_per_side=2, device='gpu', dtype=np.float64)
+    b64.zero_rhs(8, 4, dtype=np.float64)
+    assert b64.X_halo_lo.dtype == torch.float64
+
+
+def test_make_backend_gpu_f64_and_other_dtypes():
+    _need_gpu()
+    from arrow_matrix_amd.backends import make_backend
+    be = make_backend('gpu', np.float64)
+    assert be.np_dtype == np.float64 and be.torch_dtype == torch.float64
+    assert be.zeros((2, 3)).dtype == torch.float64
+    assert be.asarray(np.ones((2, 2), dtype=np.float32)).dtype == torch.float64
+    with pytest.raises(NotImplementedError):
+        make_backend('gpu', np.float16)
+
+
+def test_petsc_gpu_f64():
+    _need_gpu()
+    from scipy import sparse
+    from arrow_matrix_amd.matrix_slice import MatrixSlice
+    from arrow_matrix_amd.spmm_petsc import SpmmPETSc
+    rng = np.random.RandomState(3)
+    A = sparse.csr_matrix(sparse.random(200, 200, density=0.05,
+                                        random_state=rng, format='csr'),
+                          dtype=np.float64)
+    ms = MatrixSlice.initialize(None, A)
+    eng = SpmmPETSc(None, ms, device='gpu', dtype=np.float64)
+    X = rng.rand(200, 6)
+    Y = eng.spmm(X)
+    assert Y.dtype == torch.float64
+    np.testing.assert_allclose(Y.cpu().numpy(), A @ X, rtol=1e-12, atol=1e-12)
+
+
+def test_bench_spmm_gpu_f64():
+    _need_gpu()
+    from arrow_matrix_amd.arrow_bench import bench_spmm
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        try:
+            os.chdir(td)
+            arrow = bench_spmm(None, 64, 8, 2, True, 'gpu',
+                               datatype=np.float64)
+            assert arrow is not None
+            C = arrow.B.allgather_result()
+            assert C.dtype == np.float64
+            assert np.isfinite(C).all() and np.abs(C).max() > 0
+        finally:
+            os.chdir(cwd)
