@@ -5,7 +5,13 @@
 // gathers (arrow_dec_mpi.py:421-437,526-544). See include/arrow_spmm.h for
 // the ABI contract.
 //
-// Kernel design (CSR x tall-skinny dense, fp32, k = 1..128 typical):
+// float32 and float64 share every kernel and the launch path: the code is
+// written once over the element type, and Prec<T> below holds the little
+// that differs. A change to the shared body is checked against the build
+// before it with tools/isa_diff.py (gfx950 assembly, kernel by kernel).
+//
+// Kernel design (CSR x tall-skinny dense, k = 1..128 typical; figures are
+// for fp32, a float64 lane carries the same 16 bytes as double2):
 //   * The path is HBM-bandwidth-bound (AI ~= 2.3 flop/byte), not a dense
 //     contraction -> no MFMA. The levers are coalescing and load balance.
 //   * k is mapped across lanes of a 64-wide wavefront in GROUP-lane
@@ -35,6 +41,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -92,195 +99,292 @@ std::unordered_map<int64_t, CsrBlock> g_blocks;
 int64_t g_next_handle = 1;
 
 // ---------------------------------------------------------------------------
-// SpMM kernel.  GROUP lanes x VEC floats cover min(k, GROUP*VEC) columns;
-// wider k is handled by a column-offset loop over launches (col_off).
-// The per-item body is shared by the two schedulers below (grid-stride and
-// per-XCD queue) — spmm_process_item computes one work item end to end.
+// SpMM kernel, float and double.  GROUP lanes x VEC elements cover
+// min(k, GROUP*VEC) columns; wider k is handled by a column-offset loop over
+// launches (col_off). A lane covers at most 16 bytes of an X row: float4, or
+// double2 (the same bytes). Accumulation is fma in T; split rows add with
+// the hardware global atomic of T.
+// The per-item body is shared by the three schedulers below (grid-stride,
+// block-grab and wave-grab per-XCD queue) — spmm_process_item computes one
+// work item end to end.
 // ---------------------------------------------------------------------------
 
-template <int VEC, int GROUP, int BETA, bool GUARD>
-__device__ __forceinline__ void spmm_process_item(
-    const int2 *__restrict__ pairs, int32_t row_raw, int32_t b, int32_t e,
-    const float *__restrict__ X0, const float *__restrict__ X1,
-    float *__restrict__ C, int64_t k, int64_t col0, bool active,
-    int lane_in_group, int nt_mode) {
-  {
-    const int32_t row = row_raw & 0x7fffffff;
-    const bool is_split = row_raw < 0;
+// What differs between the two precisions, and nothing else. The A stream
+// reaches the kernels as plain `const A *__restrict__...` parameters (the
+// pack A... is {int2} for float, {int32_t, double} for double), so each
+// precision keeps its own kernarg layout and its restrict information.
+//   float : (col, val) packed 8-byte pairs, one 8-B load per lane per GROUP
+//           nonzeros; the value is one shuffle.
+//   double: SPLIT arrays int32 cols[] + double vals[] (12 B/nnz; a padded
+//           16-byte record would waste a third of the A stream), a
+//           coalesced 4-B and a coalesced 8-B load per GROUP nonzeros; the
+//           64-bit value travels as two 32-bit shuffles.
+template <typename T> struct Prec;
 
-    float acc[VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) acc[j] = 0.0f;
-
-    // Stage GROUP (col,val) pairs cooperatively (ONE coalesced 8-B/lane
-    // load per GROUP nonzeros), then broadcast them across the group with
-    // wave shuffles — the A stream costs 1/GROUP memory instructions per
-    // nonzero instead of 2.
-    auto xaddr = [&](int2 mine, int u) {
-      const int32_t c = __shfl(mine.x, u, GROUP);
-      return (c < 0 ? X1 + (int64_t)(-c - 1) * k : X0 + (int64_t)c * k) + col0;
-    };
-    auto val = [&](int2 mine, int u) {
-      return __int_as_float(__shfl(mine.y, u, GROUP));
-    };
-    auto consume = [&](int2 mine, int u) {
-      const float *xr = xaddr(mine, u);
-      const float v = val(mine, u);
-      if (active) {
-        if constexpr (VEC == 4) {
-          const float4 xv = *reinterpret_cast<const float4 *>(xr);
-          acc[0] = fmaf(v, xv.x, acc[0]);
-          acc[1] = fmaf(v, xv.y, acc[1]);
-          acc[2] = fmaf(v, xv.z, acc[2]);
-          acc[3] = fmaf(v, xv.w, acc[3]);
-        } else if constexpr (VEC == 2) {
-          const float2 xv = *reinterpret_cast<const float2 *>(xr);
-          acc[0] = fmaf(v, xv.x, acc[0]);
-          acc[1] = fmaf(v, xv.y, acc[1]);
-        } else {
-          acc[0] = fmaf(v, xr[0], acc[0]);
-        }
-      }
-    };
-    // 4 entries at a time with the four X-row loads issued back to back
-    // BEFORE any use: the rolled one-at-a-time loop stalls on each load's
-    // s_waitcnt before the next can issue (in-order issue), which makes
-    // short power-law rows latency-bound.
-    auto consume4 = [&](int2 mine, int u) {
-      if constexpr (VEC == 4) {
-        const float *p0 = xaddr(mine, u + 0);
-        const float *p1 = xaddr(mine, u + 1);
-        const float *p2 = xaddr(mine, u + 2);
-        const float *p3 = xaddr(mine, u + 3);
-        const float v0 = val(mine, u + 0), v1 = val(mine, u + 1);
-        const float v2 = val(mine, u + 2), v3 = val(mine, u + 3);
-        if (active) {
-          const float4 a0 = *reinterpret_cast<const float4 *>(p0);
-          const float4 a1 = *reinterpret_cast<const float4 *>(p1);
-          const float4 a2 = *reinterpret_cast<const float4 *>(p2);
-          const float4 a3 = *reinterpret_cast<const float4 *>(p3);
-          acc[0] = fmaf(v0, a0.x, acc[0]); acc[1] = fmaf(v0, a0.y, acc[1]);
-          acc[2] = fmaf(v0, a0.z, acc[2]); acc[3] = fmaf(v0, a0.w, acc[3]);
-          acc[0] = fmaf(v1, a1.x, acc[0]); acc[1] = fmaf(v1, a1.y, acc[1]);
-          acc[2] = fmaf(v1, a1.z, acc[2]); acc[3] = fmaf(v1, a1.w, acc[3]);
-          acc[0] = fmaf(v2, a2.x, acc[0]); acc[1] = fmaf(v2, a2.y, acc[1]);
-          acc[2] = fmaf(v2, a2.z, acc[2]); acc[3] = fmaf(v2, a2.w, acc[3]);
-          acc[0] = fmaf(v3, a3.x, acc[0]); acc[1] = fmaf(v3, a3.y, acc[1]);
-          acc[2] = fmaf(v3, a3.z, acc[2]); acc[3] = fmaf(v3, a3.w, acc[3]);
-        }
-      } else {
-        consume(mine, u); consume(mine, u + 1);
-        consume(mine, u + 2); consume(mine, u + 3);
-      }
-    };
-    // 8 loads in flight: a deg-8 power-law row issues its entire X-row
-    // load set before any use (the 4-deep batch still serialises pairs of
-    // batches on in-order issue)
-    auto consume8 = [&](int2 mine, int u) {
-      if constexpr (VEC == 4 && GROUP >= 8) {
-        const float *p[8];
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          p[j] = xaddr(mine, u + j);
-          v[j] = val(mine, u + j);
-        }
-        if (active) {
-          float4 a[8];
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            a[j] = *reinterpret_cast<const float4 *>(p[j]);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            acc[0] = fmaf(v[j], a[j].x, acc[0]);
-            acc[1] = fmaf(v[j], a[j].y, acc[1]);
-            acc[2] = fmaf(v[j], a[j].z, acc[2]);
-            acc[3] = fmaf(v[j], a[j].w, acc[3]);
-          }
-        }
-      } else {
-        consume4(mine, u);
-        consume4(mine, u + 4);
-      }
-    };
-    // nontemporal A-stream load (each pair is read once by one wave): the
-    // builtin wants a native vector type, HIP's int2 is a class
+template <> struct Prec<float> {
+  static constexpr int dtype = 32;
+  static constexpr const char *suffix = "";
+  using Staged = int2;  // one staged nonzero per lane
+  // nontemporal A-stream load (each pair is read once by one wave): the
+  // builtin wants a native vector type, HIP's int2 is a class
+  __device__ static __forceinline__ Staged load(int nt, int32_t idx,
+                                                const int2 *pairs) {
     typedef int nt_int2 __attribute__((ext_vector_type(2)));
-    auto load_pair = [&](int32_t idx) -> int2 {
-      if (nt_mode) {
-        const nt_int2 raw = __builtin_nontemporal_load(
-            reinterpret_cast<const nt_int2 *>(pairs + idx));
-        return int2{raw.x, raw.y};
-      }
-      return pairs[idx];
-    };
-    int32_t base = b;
-    for (; base + GROUP <= e; base += GROUP) {  // full chunks
-      const int2 mine = load_pair(base + lane_in_group);
-      if constexpr (GROUP >= 8) {
-#pragma unroll
-        for (int u = 0; u < GROUP; u += 8) consume8(mine, u);
-      } else if constexpr (GROUP >= 4) {
-#pragma unroll
-        for (int u = 0; u < GROUP; u += 4) consume4(mine, u);
-      } else {
-#pragma unroll
-        for (int u = 0; u < GROUP; ++u) consume(mine, u);
-      }
+    if (nt) {
+      const nt_int2 raw = __builtin_nontemporal_load(
+          reinterpret_cast<const nt_int2 *>(pairs + idx));
+      return int2{raw.x, raw.y};
     }
-    if (base < e) {  // remainder (< GROUP entries)
-      const int32_t t = base + lane_in_group;
-      const int2 mine = (t < e) ? pairs[t] : int2{0, 0};
-      const int cnt = e - base;
-      int u = 0;
-      if constexpr (GROUP >= 8) {
-        for (; u + 8 <= cnt; u += 8) consume8(mine, u);
-      }
-      for (; u + 4 <= cnt; u += 4) consume4(mine, u);
-      for (; u < cnt; ++u) consume(mine, u);
-    }
+    return pairs[idx];
+  }
+  template <int GROUP>
+  __device__ static __forceinline__ int32_t col(const Staged &mine, int u) {
+    return __shfl(mine.x, u, GROUP);
+  }
+  template <int GROUP>
+  __device__ static __forceinline__ float val(const Staged &mine, int u) {
+    return __int_as_float(__shfl(mine.y, u, GROUP));
+  }
+  __device__ static __forceinline__ float mad(float a, float b, float c) {
+    return fmaf(a, b, c);
+  }
+  template <typename F> static int with_stream(const CsrBlock &blk, F f) {
+    return f(blk.pairs);
+  }
+};
 
+template <> struct Prec<double> {
+  static constexpr int dtype = 64;
+  static constexpr const char *suffix = "_f64";
+  struct Staged { int32_t c, lo, hi; };
+  __device__ static __forceinline__ Staged load(int nt, int32_t idx,
+                                                const int32_t *cols,
+                                                const double *vals) {
+    int32_t c;
+    double v;
+    if (nt) {
+      c = __builtin_nontemporal_load(cols + idx);
+      v = __builtin_nontemporal_load(vals + idx);
+    } else {
+      c = cols[idx];
+      v = vals[idx];
+    }
+    return Staged{c, __double2loint(v), __double2hiint(v)};
+  }
+  template <int GROUP>
+  __device__ static __forceinline__ int32_t col(const Staged &mine, int u) {
+    return __shfl(mine.c, u, GROUP);
+  }
+  template <int GROUP>
+  __device__ static __forceinline__ double val(const Staged &mine, int u) {
+    return __hiloint2double(__shfl(mine.hi, u, GROUP),
+                            __shfl(mine.lo, u, GROUP));
+  }
+  __device__ static __forceinline__ double mad(double a, double b, double c) {
+    return fma(a, b, c);
+  }
+  template <typename F> static int with_stream(const CsrBlock &blk, F f) {
+    return f(blk.cols64, blk.vals64);
+  }
+};
+
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__device__ __forceinline__ void spmm_process_item(
+    int32_t row_raw, int32_t b, int32_t e, const T *__restrict__ X0,
+    const T *__restrict__ X1, T *__restrict__ C, int64_t k, int64_t col0,
+    bool active, int lane_in_group, int nt_mode, const A *__restrict__... a) {
+  using P = Prec<T>;
+  using Staged = typename P::Staged;
+  using XV = HIP_vector_type<T, VEC>;  // a lane's VEC elements of an X/C row
+  // a lane covers 16 bytes (float4 / double2): the widest load, the batched
+  // consume4 / consume8 and the vector write-back are for this layout only
+  constexpr bool LANE16 = VEC * sizeof(T) == 16;
+
+  const int32_t row = row_raw & 0x7fffffff;
+  const bool is_split = row_raw < 0;
+
+  T acc[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) acc[j] = T(0);
+
+  // Stage GROUP nonzeros cooperatively (ONE coalesced record load per lane
+  // per GROUP nonzeros), then broadcast them across the group with wave
+  // shuffles — the A stream costs 1/GROUP memory instructions per nonzero
+  // instead of 2.
+  auto xaddr = [&](const Staged &mine, int u) {
+    const int32_t c = P::template col<GROUP>(mine, u);
+    return (c < 0 ? X1 + (int64_t)(-c - 1) * k : X0 + (int64_t)c * k) + col0;
+  };
+  auto val = [&](const Staged &mine, int u) {
+    return P::template val<GROUP>(mine, u);
+  };
+  // acc += v * x, lane element by lane element
+  auto axpy = [&](T v, const XV &x) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) acc[j] = P::mad(v, x[j], acc[j]);
+  };
+  auto consume = [&](const Staged &mine, int u) {
+    const T *xr = xaddr(mine, u);
+    const T v = val(mine, u);
     if (active) {
-      float *cr = C + (int64_t)row * k + col0;
-      if (is_split) {
+      if constexpr (VEC > 1) {
+        axpy(v, *reinterpret_cast<const XV *>(xr));
+      } else {
+        acc[0] = P::mad(v, xr[0], acc[0]);
+      }
+    }
+  };
+  // 4 entries at a time with the four X-row loads issued back to back
+  // BEFORE any use: the rolled one-at-a-time loop stalls on each load's
+  // s_waitcnt before the next can issue (in-order issue), which makes
+  // short power-law rows latency-bound.
+  auto consume4 = [&](const Staged &mine, int u) {
+    if constexpr (LANE16) {
+      const T *p0 = xaddr(mine, u + 0);
+      const T *p1 = xaddr(mine, u + 1);
+      const T *p2 = xaddr(mine, u + 2);
+      const T *p3 = xaddr(mine, u + 3);
+      const T v0 = val(mine, u + 0), v1 = val(mine, u + 1);
+      const T v2 = val(mine, u + 2), v3 = val(mine, u + 3);
+      if (active) {
+        const XV a0 = *reinterpret_cast<const XV *>(p0);
+        const XV a1 = *reinterpret_cast<const XV *>(p1);
+        const XV a2 = *reinterpret_cast<const XV *>(p2);
+        const XV a3 = *reinterpret_cast<const XV *>(p3);
+        axpy(v0, a0); axpy(v1, a1); axpy(v2, a2); axpy(v3, a3);
+      }
+    } else {
+      consume(mine, u); consume(mine, u + 1);
+      consume(mine, u + 2); consume(mine, u + 3);
+    }
+  };
+  // 8 loads in flight: a deg-8 power-law row issues its entire X-row
+  // load set before any use (the 4-deep batch still serialises pairs of
+  // batches on in-order issue)
+  auto consume8 = [&](const Staged &mine, int u) {
+    if constexpr (LANE16 && GROUP >= 8) {
+      const T *p[8];
+      T v[8];
 #pragma unroll
-        for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
-      } else if constexpr (BETA == 1) {
-        if constexpr (VEC == 4) {
-          float4 old = *reinterpret_cast<float4 *>(cr);
-          old.x += acc[0]; old.y += acc[1]; old.z += acc[2]; old.w += acc[3];
-          *reinterpret_cast<float4 *>(cr) = old;
+      for (int j = 0; j < 8; ++j) {
+        p[j] = xaddr(mine, u + j);
+        v[j] = val(mine, u + j);
+      }
+      if (active) {
+        XV x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const XV *>(p[j]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) axpy(v[j], x[j]);
+      }
+    } else {
+      consume4(mine, u);
+      consume4(mine, u + 4);
+    }
+  };
+  int32_t base = b;
+  for (; base + GROUP <= e; base += GROUP) {  // full chunks
+    const Staged mine = P::load(nt_mode, base + lane_in_group, a...);
+    if constexpr (GROUP >= 8) {
+#pragma unroll
+      for (int u = 0; u < GROUP; u += 8) consume8(mine, u);
+    } else if constexpr (GROUP >= 4) {
+#pragma unroll
+      for (int u = 0; u < GROUP; u += 4) consume4(mine, u);
+    } else {
+#pragma unroll
+      for (int u = 0; u < GROUP; ++u) consume(mine, u);
+    }
+  }
+  if (base < e) {  // remainder (< GROUP entries), cached loads
+    const int32_t t = base + lane_in_group;
+    const Staged mine = (t < e) ? P::load(0, t, a...) : Staged{};
+    const int cnt = e - base;
+    int u = 0;
+    if constexpr (GROUP >= 8) {
+      for (; u + 8 <= cnt; u += 8) consume8(mine, u);
+    }
+    for (; u + 4 <= cnt; u += 4) consume4(mine, u);
+    for (; u < cnt; ++u) consume(mine, u);
+  }
+
+  if (active) {
+    T *cr = C + (int64_t)row * k + col0;
+    if (is_split) {
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
+    } else if constexpr (BETA == 1) {
+      if constexpr (LANE16) {
+        XV old = *reinterpret_cast<XV *>(cr);
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) old[j] += acc[j];
+        *reinterpret_cast<XV *>(cr) = old;
+      } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) cr[j] += acc[j];
+      }
+    } else {
+      if constexpr (LANE16) {
+        if (nt_mode) {
+          typedef T nt_vec __attribute__((ext_vector_type(VEC)));
+          nt_vec outv;
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) outv[j] = acc[j];
+          __builtin_nontemporal_store(outv, reinterpret_cast<nt_vec *>(cr));
         } else {
+          XV outv;
 #pragma unroll
-          for (int j = 0; j < VEC; ++j) cr[j] += acc[j];
+          for (int j = 0; j < VEC; ++j) outv[j] = acc[j];
+          *reinterpret_cast<XV *>(cr) = outv;
         }
       } else {
-        if constexpr (VEC == 4) {
-          if (nt_mode) {
-            typedef float nt_float4 __attribute__((ext_vector_type(4)));
-            const nt_float4 outv = {acc[0], acc[1], acc[2], acc[3]};
-            __builtin_nontemporal_store(outv,
-                                        reinterpret_cast<nt_float4 *>(cr));
-          } else {
-            *reinterpret_cast<float4 *>(cr) = float4{acc[0], acc[1], acc[2],
-                                                     acc[3]};
-          }
-        } else {
 #pragma unroll
-          for (int j = 0; j < VEC; ++j) cr[j] = acc[j];
-        }
+        for (int j = 0; j < VEC; ++j) cr[j] = acc[j];
       }
     }
   }
 }
 
-template <int VEC, int GROUP, int BETA, bool GUARD>
+// Items first, first + step, ... below end, one per row group: the loop all
+// three schedulers run over their share of the work items.
+// Software prefetch of the NEXT item's metadata: without it every ~8-nnz
+// item pays a 3-deep dependent load chain (meta -> A stream -> X row) that
+// dominates short power-law rows.
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__device__ __forceinline__ void spmm_process_items(
+    int64_t item, int64_t end, int64_t step, const int32_t *item_row,
+    const int32_t *item_begin, const int32_t *item_end, const T *X0,
+    const T *X1, T *C, int64_t k, int64_t col0, bool active,
+    int lane_in_group, int nt_mode, const A *... a) {
+  int32_t next_row = 0, next_b = 0, next_e = 0;
+  if (item < end) {
+    next_row = __builtin_nontemporal_load(&item_row[item]);
+    next_b = __builtin_nontemporal_load(&item_begin[item]);
+    next_e = __builtin_nontemporal_load(&item_end[item]);
+  }
+  for (; item < end; item += step) {
+    const int32_t row_raw = next_row;
+    const int32_t b = next_b;
+    const int32_t e = next_e;
+    const int64_t nxt = item + step;
+    if (nxt < end) {
+      next_row = __builtin_nontemporal_load(&item_row[nxt]);
+      next_b = __builtin_nontemporal_load(&item_begin[nxt]);
+      next_e = __builtin_nontemporal_load(&item_end[nxt]);
+    }
+    spmm_process_item<T, VEC, GROUP, BETA, GUARD>(
+        row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group, nt_mode,
+        a...);
+  }
+}
+
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel(
-    const int2 *__restrict__ pairs,
+    const A *__restrict__... a,
     const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
     const int32_t *__restrict__ item_end, int64_t n_items,
-    const float *__restrict__ X0, const float *__restrict__ X1,
-    float *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
     int nt_mode) {
   constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
   const int lane_in_group = threadIdx.x % GROUP;
@@ -301,33 +405,10 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel(
     wg = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + pos;
   }
 
-  int64_t item = (int64_t)wg * GROUPS_PER_BLOCK + group_in_block;
-  const int64_t stride = (int64_t)gridDim.x * GROUPS_PER_BLOCK;
-
-  // software prefetch of the NEXT item's metadata: without it every ~8-nnz
-  // item pays a 3-deep dependent load chain (meta -> pairs -> X row) that
-  // dominates short power-law rows
-  int32_t next_row = 0, next_b = 0, next_e = 0;
-  if (item < n_items) {
-    next_row = __builtin_nontemporal_load(&item_row[item]);
-    next_b = __builtin_nontemporal_load(&item_begin[item]);
-    next_e = __builtin_nontemporal_load(&item_end[item]);
-  }
-
-  for (; item < n_items; item += stride) {
-    const int32_t row_raw = next_row;
-    const int32_t b = next_b;
-    const int32_t e = next_e;
-    const int64_t nxt = item + stride;
-    if (nxt < n_items) {
-      next_row = __builtin_nontemporal_load(&item_row[nxt]);
-      next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-      next_e = __builtin_nontemporal_load(&item_end[nxt]);
-    }
-    spmm_process_item<VEC, GROUP, BETA, GUARD>(
-        pairs, row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group,
-        nt_mode);
-  }
+  spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
+      (int64_t)wg * GROUPS_PER_BLOCK + group_in_block, n_items,
+      (int64_t)gridDim.x * GROUPS_PER_BLOCK, item_row, item_begin, item_end,
+      X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
 }
 
 // Per-XCD queue scheduler. The static grid-stride schedule above interleaves
@@ -347,16 +428,16 @@ __device__ __forceinline__ unsigned arrow_xcc_id() {
   return __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
 }
 
-template <int VEC, int GROUP, int BETA, bool GUARD>
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
-    const int2 *__restrict__ pairs,
+    const A *__restrict__... a,
     const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
     const int32_t *__restrict__ item_end,
     const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
     int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
     int chunk_items,
-    const float *__restrict__ X0, const float *__restrict__ X1,
-    float *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
   constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
   const int lane_in_group = threadIdx.x % GROUP;
   const int group_in_block = threadIdx.x / GROUP;
@@ -378,27 +459,9 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
       const int64_t base = s_base;
       if (base >= hi) break;
       const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      int64_t item = base + group_in_block;
-      int32_t next_row = 0, next_b = 0, next_e = 0;
-      if (item < end) {
-        next_row = __builtin_nontemporal_load(&item_row[item]);
-        next_b = __builtin_nontemporal_load(&item_begin[item]);
-        next_e = __builtin_nontemporal_load(&item_end[item]);
-      }
-      for (; item < end; item += GROUPS_PER_BLOCK) {
-        const int32_t row_raw = next_row;
-        const int32_t b = next_b;
-        const int32_t e = next_e;
-        const int64_t nxt = item + GROUPS_PER_BLOCK;
-        if (nxt < end) {
-          next_row = __builtin_nontemporal_load(&item_row[nxt]);
-          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-          next_e = __builtin_nontemporal_load(&item_end[nxt]);
-        }
-        spmm_process_item<VEC, GROUP, BETA, GUARD>(
-            pairs, row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group,
-            nt_mode);
-      }
+      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
+          base + group_in_block, end, GROUPS_PER_BLOCK, item_row, item_begin,
+          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
     }
   }
 }
@@ -410,16 +473,16 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
 // the slowest group of all 4 waves), at the cost of 4x the atomic rate
 // (fine: per-XCD counters, dequeue ~0.25-1.1 us uncontended and these are
 // thousands of grabs per segment, MI355X_MICROARCH.md §dequeue).
-template <int VEC, int GROUP, int BETA, bool GUARD>
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw(
-    const int2 *__restrict__ pairs,
+    const A *__restrict__... a,
     const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
     const int32_t *__restrict__ item_end,
     const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
     int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
     int chunk_items,                  // per-WAVE grab size (items)
-    const float *__restrict__ X0, const float *__restrict__ X1,
-    float *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
   constexpr int GROUPS_PER_WAVE = 64 / GROUP;
   const int lane = threadIdx.x & 63;
   const int lane_in_group = threadIdx.x % GROUP;
@@ -439,385 +502,22 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw(
       const int64_t base = lo + grab;
       if (base >= hi) break;
       const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      int64_t item = base + group_in_wave;
-      int32_t next_row = 0, next_b = 0, next_e = 0;
-      if (item < end) {
-        next_row = __builtin_nontemporal_load(&item_row[item]);
-        next_b = __builtin_nontemporal_load(&item_begin[item]);
-        next_e = __builtin_nontemporal_load(&item_end[item]);
-      }
-      for (; item < end; item += GROUPS_PER_WAVE) {
-        const int32_t row_raw = next_row;
-        const int32_t b = next_b;
-        const int32_t e = next_e;
-        const int64_t nxt = item + GROUPS_PER_WAVE;
-        if (nxt < end) {
-          next_row = __builtin_nontemporal_load(&item_row[nxt]);
-          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-          next_e = __builtin_nontemporal_load(&item_end[nxt]);
-        }
-        spmm_process_item<VEC, GROUP, BETA, GUARD>(
-            pairs, row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group,
-            nt_mode);
-      }
+      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
+          base + group_in_wave, end, GROUPS_PER_WAVE, item_row, item_begin,
+          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
     }
   }
 }
 
-__global__ void zero_rows_kernel(float *__restrict__ C,
+template <typename T>
+__global__ void zero_rows_kernel(T *__restrict__ C,
                                  const int32_t *__restrict__ rows,
                                  int64_t n_rows, int64_t k) {
   const int64_t total = n_rows * k;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i = t / k, j = t % k;
-    C[(int64_t)rows[i] * k + j] = 0.0f;
-  }
-}
-
-// ---------------------------------------------------------------------------
-// float64 SpMM.  The twin of the fp32 path above, kept as separate code so
-// the fp32 instantiations stay exactly as they were. A lane covers VEC
-// doubles of an X row (double2 = one 16-byte load when k is even, the same
-// bytes per lane as the fp32 float4), GROUP lanes cover one work item, and
-// A is resident as SPLIT arrays int32 cols[] + double vals[] (12 B/nnz; a
-// padded 16-byte record would waste a third of the A stream). Accumulation
-// is double fma; split rows add with the hardware f64 global atomic.
-// ---------------------------------------------------------------------------
-
-template <int VEC, int GROUP, int BETA, bool GUARD>
-__device__ __forceinline__ void spmm_process_item_f64(
-    const int32_t *__restrict__ cols, const double *__restrict__ vals,
-    int32_t row_raw, int32_t b, int32_t e,
-    const double *__restrict__ X0, const double *__restrict__ X1,
-    double *__restrict__ C, int64_t k, int64_t col0, bool active,
-    int lane_in_group, int nt_mode) {
-  const int32_t row = row_raw & 0x7fffffff;
-  const bool is_split = row_raw < 0;
-
-  double acc[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) acc[j] = 0.0;
-
-  // One staged nonzero per lane: GROUP (col, val) entries are loaded
-  // cooperatively (a coalesced 4-B and a coalesced 8-B load per GROUP
-  // nonzeros) and broadcast with wave shuffles; the 64-bit value travels
-  // as two 32-bit shuffles.
-  struct Staged { int32_t c, lo, hi; };
-  auto xaddr = [&](const Staged &mine, int u) {
-    const int32_t c = __shfl(mine.c, u, GROUP);
-    return (c < 0 ? X1 + (int64_t)(-c - 1) * k : X0 + (int64_t)c * k) + col0;
-  };
-  auto val = [&](const Staged &mine, int u) {
-    return __hiloint2double(__shfl(mine.hi, u, GROUP),
-                            __shfl(mine.lo, u, GROUP));
-  };
-  auto consume = [&](const Staged &mine, int u) {
-    const double *xr = xaddr(mine, u);
-    const double v = val(mine, u);
-    if (active) {
-      if constexpr (VEC == 2) {
-        const double2 xv = *reinterpret_cast<const double2 *>(xr);
-        acc[0] = fma(v, xv.x, acc[0]);
-        acc[1] = fma(v, xv.y, acc[1]);
-      } else {
-        acc[0] = fma(v, xr[0], acc[0]);
-      }
-    }
-  };
-  // 4 entries at a time, the four X-row loads issued back to back BEFORE
-  // any use (see the fp32 body: in-order issue stalls a rolled loop on each
-  // load's s_waitcnt)
-  auto consume4 = [&](const Staged &mine, int u) {
-    if constexpr (VEC == 2) {
-      const double *p0 = xaddr(mine, u + 0);
-      const double *p1 = xaddr(mine, u + 1);
-      const double *p2 = xaddr(mine, u + 2);
-      const double *p3 = xaddr(mine, u + 3);
-      const double v0 = val(mine, u + 0), v1 = val(mine, u + 1);
-      const double v2 = val(mine, u + 2), v3 = val(mine, u + 3);
-      if (active) {
-        const double2 a0 = *reinterpret_cast<const double2 *>(p0);
-        const double2 a1 = *reinterpret_cast<const double2 *>(p1);
-        const double2 a2 = *reinterpret_cast<const double2 *>(p2);
-        const double2 a3 = *reinterpret_cast<const double2 *>(p3);
-        acc[0] = fma(v0, a0.x, acc[0]); acc[1] = fma(v0, a0.y, acc[1]);
-        acc[0] = fma(v1, a1.x, acc[0]); acc[1] = fma(v1, a1.y, acc[1]);
-        acc[0] = fma(v2, a2.x, acc[0]); acc[1] = fma(v2, a2.y, acc[1]);
-        acc[0] = fma(v3, a3.x, acc[0]); acc[1] = fma(v3, a3.y, acc[1]);
-      }
-    } else {
-      consume(mine, u); consume(mine, u + 1);
-      consume(mine, u + 2); consume(mine, u + 3);
-    }
-  };
-  // 8 loads in flight (a deg-8 power-law row issues its whole X-row load
-  // set before any use)
-  auto consume8 = [&](const Staged &mine, int u) {
-    if constexpr (VEC == 2 && GROUP >= 8) {
-      const double *p[8];
-      double v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        p[j] = xaddr(mine, u + j);
-        v[j] = val(mine, u + j);
-      }
-      if (active) {
-        double2 a[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          a[j] = *reinterpret_cast<const double2 *>(p[j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          acc[0] = fma(v[j], a[j].x, acc[0]);
-          acc[1] = fma(v[j], a[j].y, acc[1]);
-        }
-      }
-    } else {
-      consume4(mine, u);
-      consume4(mine, u + 4);
-    }
-  };
-  // non-temporal A-stream loads (each entry is read once by one wave)
-  auto load_stage = [&](int32_t idx) -> Staged {
-    int32_t c;
-    double v;
-    if (nt_mode) {
-      c = __builtin_nontemporal_load(cols + idx);
-      v = __builtin_nontemporal_load(vals + idx);
-    } else {
-      c = cols[idx];
-      v = vals[idx];
-    }
-    return Staged{c, __double2loint(v), __double2hiint(v)};
-  };
-  int32_t base = b;
-  for (; base + GROUP <= e; base += GROUP) {  // full chunks
-    const Staged mine = load_stage(base + lane_in_group);
-    if constexpr (GROUP >= 8) {
-#pragma unroll
-      for (int u = 0; u < GROUP; u += 8) consume8(mine, u);
-    } else if constexpr (GROUP >= 4) {
-#pragma unroll
-      for (int u = 0; u < GROUP; u += 4) consume4(mine, u);
-    } else {
-#pragma unroll
-      for (int u = 0; u < GROUP; ++u) consume(mine, u);
-    }
-  }
-  if (base < e) {  // remainder (< GROUP entries)
-    const int32_t t = base + lane_in_group;
-    Staged mine{0, 0, 0};
-    if (t < e) {
-      const double v = vals[t];
-      mine = Staged{cols[t], __double2loint(v), __double2hiint(v)};
-    }
-    const int cnt = e - base;
-    int u = 0;
-    if constexpr (GROUP >= 8) {
-      for (; u + 8 <= cnt; u += 8) consume8(mine, u);
-    }
-    for (; u + 4 <= cnt; u += 4) consume4(mine, u);
-    for (; u < cnt; ++u) consume(mine, u);
-  }
-
-  if (active) {
-    double *cr = C + (int64_t)row * k + col0;
-    if (is_split) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
-    } else if constexpr (BETA == 1) {
-      if constexpr (VEC == 2) {
-        double2 old = *reinterpret_cast<double2 *>(cr);
-        old.x += acc[0]; old.y += acc[1];
-        *reinterpret_cast<double2 *>(cr) = old;
-      } else {
-        cr[0] += acc[0];
-      }
-    } else {
-      if constexpr (VEC == 2) {
-        if (nt_mode) {
-          typedef double nt_double2 __attribute__((ext_vector_type(2)));
-          const nt_double2 outv = {acc[0], acc[1]};
-          __builtin_nontemporal_store(outv, reinterpret_cast<nt_double2 *>(cr));
-        } else {
-          *reinterpret_cast<double2 *>(cr) = double2{acc[0], acc[1]};
-        }
-      } else {
-        cr[0] = acc[0];
-      }
-    }
-  }
-}
-
-// The three schedulers, as for fp32 (grid-stride, block-grab queue,
-// wave-grab queue); see the comments on spmm_kernel / _q / _qw.
-template <int VEC, int GROUP, int BETA, bool GUARD>
-__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_f64(
-    const int32_t *__restrict__ cols, const double *__restrict__ vals,
-    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
-    const int32_t *__restrict__ item_end, int64_t n_items,
-    const double *__restrict__ X0, const double *__restrict__ X1,
-    double *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
-    int nt_mode) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_block = threadIdx.x / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
-
-  int wg = blockIdx.x;
-  if (xcd_remap) {
-    const int nwg = gridDim.x;
-    const int q = nwg / 8, rm = nwg % 8;
-    const int xcd = blockIdx.x % 8, pos = blockIdx.x / 8;
-    wg = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + pos;
-  }
-
-  int64_t item = (int64_t)wg * GROUPS_PER_BLOCK + group_in_block;
-  const int64_t stride = (int64_t)gridDim.x * GROUPS_PER_BLOCK;
-
-  int32_t next_row = 0, next_b = 0, next_e = 0;
-  if (item < n_items) {
-    next_row = __builtin_nontemporal_load(&item_row[item]);
-    next_b = __builtin_nontemporal_load(&item_begin[item]);
-    next_e = __builtin_nontemporal_load(&item_end[item]);
-  }
-
-  for (; item < n_items; item += stride) {
-    const int32_t row_raw = next_row;
-    const int32_t b = next_b;
-    const int32_t e = next_e;
-    const int64_t nxt = item + stride;
-    if (nxt < n_items) {
-      next_row = __builtin_nontemporal_load(&item_row[nxt]);
-      next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-      next_e = __builtin_nontemporal_load(&item_end[nxt]);
-    }
-    spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
-        cols, vals, row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group,
-        nt_mode);
-  }
-}
-
-template <int VEC, int GROUP, int BETA, bool GUARD>
-__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q_f64(
-    const int32_t *__restrict__ cols, const double *__restrict__ vals,
-    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
-    const int32_t *__restrict__ item_end,
-    const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
-    int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
-    int chunk_items,
-    const double *__restrict__ X0, const double *__restrict__ X1,
-    double *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_block = threadIdx.x / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
-  __shared__ int64_t s_base;
-
-  const unsigned q0 = arrow_xcc_id() & 7;
-  for (unsigned qi = 0; qi < 8; ++qi) {
-    const unsigned q = (q0 + qi) & 7;
-    const int64_t lo = qseg[q], hi = qseg[q + 1];
-    if (lo >= hi) continue;
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        s_base = lo + (int64_t)atomicAdd(&qctr[q * 32], chunk_items);
-      }
-      __syncthreads();
-      const int64_t base = s_base;
-      if (base >= hi) break;
-      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      int64_t item = base + group_in_block;
-      int32_t next_row = 0, next_b = 0, next_e = 0;
-      if (item < end) {
-        next_row = __builtin_nontemporal_load(&item_row[item]);
-        next_b = __builtin_nontemporal_load(&item_begin[item]);
-        next_e = __builtin_nontemporal_load(&item_end[item]);
-      }
-      for (; item < end; item += GROUPS_PER_BLOCK) {
-        const int32_t row_raw = next_row;
-        const int32_t b = next_b;
-        const int32_t e = next_e;
-        const int64_t nxt = item + GROUPS_PER_BLOCK;
-        if (nxt < end) {
-          next_row = __builtin_nontemporal_load(&item_row[nxt]);
-          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-          next_e = __builtin_nontemporal_load(&item_end[nxt]);
-        }
-        spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
-            cols, vals, row_raw, b, e, X0, X1, C, k, col0, active,
-            lane_in_group, nt_mode);
-      }
-    }
-  }
-}
-
-template <int VEC, int GROUP, int BETA, bool GUARD>
-__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw_f64(
-    const int32_t *__restrict__ cols, const double *__restrict__ vals,
-    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
-    const int32_t *__restrict__ item_end,
-    const int64_t *__restrict__ qseg,  // 9 segment bounds (items)
-    int32_t *__restrict__ qctr,       // 8 counters, padded 32 ints apart
-    int chunk_items,                  // per-WAVE grab size (items)
-    const double *__restrict__ X0, const double *__restrict__ X1,
-    double *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
-  constexpr int GROUPS_PER_WAVE = 64 / GROUP;
-  const int lane = threadIdx.x & 63;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_wave = lane / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
-
-  const unsigned q0 = arrow_xcc_id() & 7;
-  for (unsigned qi = 0; qi < 8; ++qi) {
-    const unsigned q = (q0 + qi) & 7;
-    const int64_t lo = qseg[q], hi = qseg[q + 1];
-    if (lo >= hi) continue;
-    for (;;) {
-      int grab = 0;
-      if (lane == 0) grab = atomicAdd(&qctr[q * 32], chunk_items);
-      grab = __shfl(grab, 0, 64);
-      const int64_t base = lo + grab;
-      if (base >= hi) break;
-      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      int64_t item = base + group_in_wave;
-      int32_t next_row = 0, next_b = 0, next_e = 0;
-      if (item < end) {
-        next_row = __builtin_nontemporal_load(&item_row[item]);
-        next_b = __builtin_nontemporal_load(&item_begin[item]);
-        next_e = __builtin_nontemporal_load(&item_end[item]);
-      }
-      for (; item < end; item += GROUPS_PER_WAVE) {
-        const int32_t row_raw = next_row;
-        const int32_t b = next_b;
-        const int32_t e = next_e;
-        const int64_t nxt = item + GROUPS_PER_WAVE;
-        if (nxt < end) {
-          next_row = __builtin_nontemporal_load(&item_row[nxt]);
-          next_b = __builtin_nontemporal_load(&item_begin[nxt]);
-          next_e = __builtin_nontemporal_load(&item_end[nxt]);
-        }
-        spmm_process_item_f64<VEC, GROUP, BETA, GUARD>(
-            cols, vals, row_raw, b, e, X0, X1, C, k, col0, active,
-            lane_in_group, nt_mode);
-      }
-    }
-  }
-}
-
-__global__ void zero_rows_kernel_f64(double *__restrict__ C,
-                                     const int32_t *__restrict__ rows,
-                                     int64_t n_rows, int64_t k) {
-  const int64_t total = n_rows * k;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = t / k, j = t % k;
-    C[(int64_t)rows[i] * k + j] = 0.0;
+    C[(int64_t)rows[i] * k + j] = T(0);
   }
 }
 
@@ -827,12 +527,32 @@ __global__ void zero_rows_kernel_f64(double *__restrict__ C,
 
 enum class RouteOp { Gather, Scatter, ScatterAdd };
 
-template <typename VT, RouteOp OP>
-__global__ void route_rows_kernel(float *__restrict__ dst,
-                                  const float *__restrict__ src,
+// A lane moves N elements of T: 16 bytes when k allows, else one element.
+// The float64 pure copies run the float kernels on rows of 2k floats, so
+// only the adding forms are instantiated for double.
+template <typename T, int N>
+using RouteVec = std::conditional_t<N == 1, T, HIP_vector_type<T, N>>;
+
+template <typename T, int N>
+__device__ __forceinline__ void route_add(RouteVec<T, N> *d,
+                                          const RouteVec<T, N> &v) {
+  if constexpr (N == 1) {
+    *d += v;
+  } else {
+    RouteVec<T, N> b = *d;
+#pragma unroll
+    for (int j = 0; j < N; ++j) b[j] += v[j];
+    *d = b;
+  }
+}
+
+template <typename T, int N, RouteOp OP>
+__global__ void route_rows_kernel(T *__restrict__ dst,
+                                  const T *__restrict__ src,
                                   const int64_t *__restrict__ idx, int64_t n,
                                   int64_t k_vec) {
-  // k_vec = k / (elements per VT); row r maps dst<->src[idx[r]]
+  // k_vec = k / N; row r maps dst<->src[idx[r]]
+  using VT = RouteVec<T, N>;
   const int64_t total = n * k_vec;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
@@ -845,15 +565,7 @@ __global__ void route_rows_kernel(float *__restrict__ dst,
           reinterpret_cast<const VT *>(src)[i * k_vec + j];
     } else {
       const VT v = reinterpret_cast<const VT *>(src)[i * k_vec + j];
-      VT *d = reinterpret_cast<VT *>(dst) + idx[i] * k_vec + j;
-      if constexpr (sizeof(VT) == 4) {
-        *d += v;
-      } else {
-        const float4 a = *reinterpret_cast<const float4 *>(&v);
-        float4 b = *reinterpret_cast<float4 *>(d);
-        b.x += a.x; b.y += a.y; b.z += a.z; b.w += a.w;
-        *reinterpret_cast<float4 *>(d) = b;
-      }
+      route_add<T, N>(reinterpret_cast<VT *>(dst) + idx[i] * k_vec + j, v);
     }
   }
 }
@@ -861,59 +573,51 @@ __global__ void route_rows_kernel(float *__restrict__ dst,
 // dst[dst_idx[i], :] (+)= src[src_idx[i], :] — fused gather+scatter for the
 // rank-local share of the permutation exchange (one read + one write per
 // element instead of a gather pass plus a scatter pass).
-template <typename VT, bool ADD>
-__global__ void permute_rows_kernel(float *__restrict__ dst,
-                                    const float *__restrict__ src,
+template <typename T, int N, bool ADD>
+__global__ void permute_rows_kernel(T *__restrict__ dst,
+                                    const T *__restrict__ src,
                                     const int64_t *__restrict__ dst_idx,
                                     const int64_t *__restrict__ src_idx,
                                     int64_t n, int64_t k_vec) {
+  using VT = RouteVec<T, N>;
   const int64_t total = n * k_vec;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
        t += (int64_t)gridDim.x * blockDim.x) {
     const int64_t i = t / k_vec, j = t % k_vec;
     const VT v = reinterpret_cast<const VT *>(src)[src_idx[i] * k_vec + j];
     VT *d = reinterpret_cast<VT *>(dst) + dst_idx[i] * k_vec + j;
-    if constexpr (!ADD) {
-      *d = v;
-    } else if constexpr (sizeof(VT) == 4) {
-      *d += v;
-    } else {
-      const float4 a = *reinterpret_cast<const float4 *>(&v);
-      float4 b = *reinterpret_cast<float4 *>(d);
-      b.x += a.x; b.y += a.y; b.z += a.z; b.w += a.w;
-      *reinterpret_cast<float4 *>(d) = b;
-    }
+    if constexpr (ADD) route_add<T, N>(d, v);
+    else               *d = v;
   }
 }
 
-int launch_permute(int add, float *dst, const float *src, const int64_t *dst_idx,
+template <typename T, bool ADD>
+int launch_permute(T *dst, const T *src, const int64_t *dst_idx,
                    const int64_t *src_idx, int64_t n, int64_t k,
                    hipStream_t stream) {
   if (n == 0) return 0;
-  const bool vec4 = (k % 4 == 0);
-  const int64_t k_vec = vec4 ? k / 4 : k;
+  constexpr int N = 16 / sizeof(T);
+  const bool vec = (k % N == 0);
+  const int64_t k_vec = vec ? k / N : k;
   const int threads = 256;
   int blocks = (int)std::min<int64_t>((n * k_vec + threads - 1) / threads, 16384);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, dst, src,
                        dst_idx, src_idx, n, k_vec);
   };
-  if (vec4) {
-    if (add) launch(permute_rows_kernel<float4, true>);
-    else     launch(permute_rows_kernel<float4, false>);
-  } else {
-    if (add) launch(permute_rows_kernel<float, true>);
-    else     launch(permute_rows_kernel<float, false>);
-  }
+  if (vec) launch(permute_rows_kernel<T, N, ADD>);
+  else     launch(permute_rows_kernel<T, 1, ADD>);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
 
-int launch_route(RouteOp op, float *dst, const float *src, const int64_t *idx,
-                 int64_t n, int64_t k, hipStream_t stream) {
+template <typename T, RouteOp OP>
+int launch_route(T *dst, const T *src, const int64_t *idx, int64_t n,
+                 int64_t k, hipStream_t stream) {
   if (n == 0) return 0;
-  const bool vec4 = (k % 4 == 0);
-  const int64_t k_vec = vec4 ? k / 4 : k;
+  constexpr int N = 16 / sizeof(T);
+  const bool vec = (k % N == 0);
+  const int64_t k_vec = vec ? k / N : k;
   const int64_t total = n * k_vec;
   const int threads = 256;
   int blocks = (int)std::min<int64_t>((total + threads - 1) / threads, 16384);
@@ -921,64 +625,8 @@ int launch_route(RouteOp op, float *dst, const float *src, const int64_t *idx,
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, dst, src,
                        idx, n, k_vec);
   };
-  if (vec4) {
-    switch (op) {
-      case RouteOp::Gather: launch(route_rows_kernel<float4, RouteOp::Gather>); break;
-      case RouteOp::Scatter: launch(route_rows_kernel<float4, RouteOp::Scatter>); break;
-      case RouteOp::ScatterAdd: launch(route_rows_kernel<float4, RouteOp::ScatterAdd>); break;
-    }
-  } else {
-    switch (op) {
-      case RouteOp::Gather: launch(route_rows_kernel<float, RouteOp::Gather>); break;
-      case RouteOp::Scatter: launch(route_rows_kernel<float, RouteOp::Scatter>); break;
-      case RouteOp::ScatterAdd: launch(route_rows_kernel<float, RouteOp::ScatterAdd>); break;
-    }
-  }
-  HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-// float64 adding routes: dst[dst_idx[i], :] += src[s, :] with s = src_idx[i]
-// (permute-add) or s = i when src_idx is null (scatter-add). The three pure
-// f64 copies reuse the fp32 kernels with each row viewed as 2k floats.
-template <int VEC>
-__global__ void route_add_rows_f64_kernel(double *__restrict__ dst,
-                                          const double *__restrict__ src,
-                                          const int64_t *__restrict__ dst_idx,
-                                          const int64_t *__restrict__ src_idx,
-                                          int64_t n, int64_t k_vec) {
-  const int64_t total = n * k_vec;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
-       t += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t i = t / k_vec, j = t % k_vec;
-    const int64_t s = src_idx ? src_idx[i] : i;
-    if constexpr (VEC == 2) {
-      const double2 a = reinterpret_cast<const double2 *>(src)[s * k_vec + j];
-      double2 *d = reinterpret_cast<double2 *>(dst) + dst_idx[i] * k_vec + j;
-      double2 b = *d;
-      b.x += a.x; b.y += a.y;
-      *d = b;
-    } else {
-      dst[dst_idx[i] * k_vec + j] += src[s * k_vec + j];
-    }
-  }
-}
-
-int launch_route_add_f64(double *dst, const double *src, const int64_t *dst_idx,
-                         const int64_t *src_idx, int64_t n, int64_t k,
-                         hipStream_t stream) {
-  if (n == 0) return 0;
-  const bool vec2 = (k % 2 == 0);
-  const int64_t k_vec = vec2 ? k / 2 : k;
-  const int threads = 256;
-  int blocks = (int)std::min<int64_t>((n * k_vec + threads - 1) / threads, 16384);
-  if (vec2) {
-    hipLaunchKernelGGL(route_add_rows_f64_kernel<2>, dim3(blocks), dim3(threads),
-                       0, stream, dst, src, dst_idx, src_idx, n, k_vec);
-  } else {
-    hipLaunchKernelGGL(route_add_rows_f64_kernel<1>, dim3(blocks), dim3(threads),
-                       0, stream, dst, src, dst_idx, src_idx, n, k_vec);
-  }
+  if (vec) launch(route_rows_kernel<T, N, OP>);
+  else     launch(route_rows_kernel<T, 1, OP>);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -1069,23 +717,19 @@ struct SpmmPlan {
   int n_launches;   // col_off launches = ceil(k / (group * vec))
 };
 
-void pick_cfg(int64_t k, int *vec_out, int *group_out) {
+// A lane holds VEC elements, 16 bytes when k allows: float4 / double2.
+// ARROW_SPMM_G64 / ARROW_K16_G8 are fp32 layout experiments and do not
+// apply to float64.
+void pick_cfg(int64_t k, int dtype, int *vec_out, int *group_out) {
   const SpmmEnv &env = spmm_env();
-  if (env.g64 && k == 128) { *vec_out = 2; *group_out = 64; return; }
-  if (env.k16g8 && k == 16) { *vec_out = 2; *group_out = 8; return; }
-  int vec = (k % 4 == 0) ? 4 : (k % 2 == 0) ? 2 : 1;
-  int64_t lanes_needed = (k + vec - 1) / vec;
-  int group = 1;
-  while (group < lanes_needed && group < 64) group <<= 1;
-  *vec_out = vec;
-  *group_out = group;
-}
-
-// float64: a lane holds VEC doubles — double2 (16 B, the bytes of the fp32
-// float4) when k is even. ARROW_SPMM_G64 / ARROW_K16_G8 are fp32 layout
-// experiments and do not apply.
-void pick_cfg_f64(int64_t k, int *vec_out, int *group_out) {
-  const int vec = (k % 2 == 0) ? 2 : 1;
+  int vec;
+  if (dtype == 64) {
+    vec = (k % 2 == 0) ? 2 : 1;
+  } else {
+    if (env.g64 && k == 128) { *vec_out = 2; *group_out = 64; return; }
+    if (env.k16g8 && k == 16) { *vec_out = 2; *group_out = 8; return; }
+    vec = (k % 4 == 0) ? 4 : (k % 2 == 0) ? 2 : 1;
+  }
   const int64_t lanes_needed = (k + vec - 1) / vec;
   int group = 1;
   while (group < lanes_needed && group < 64) group <<= 1;
@@ -1102,8 +746,7 @@ SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
                    int q_blocks_override, int dtype = 32) {
   const SpmmEnv &env = spmm_env();
   SpmmPlan p;
-  if (dtype == 64) pick_cfg_f64(k, &p.vec, &p.group);
-  else             pick_cfg(k, &p.vec, &p.group);
+  pick_cfg(k, dtype, &p.vec, &p.group);
   p.nt_mode = env.nt_mode;
   const int qd = queue_mode >= 0 ? (queue_mode ? 1 : 0) : env.queue_default;
   const bool useq = qd >= 0 ? (qd == 1)
@@ -1124,16 +767,18 @@ SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
   return p;
 }
 
-template <int VEC, int GROUP>
-int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
-                   const float *X1, float *C, int64_t k, int beta,
-                   hipStream_t stream) {
+// a...: the structure's A-stream device pointers (Prec<T>::with_stream)
+template <typename T, int VEC, int GROUP, typename... A>
+int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
+                   const T *X1, T *C, int64_t k, int beta, hipStream_t stream,
+                   const A *... a) {
   constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
   const int nt_mode = plan.nt_mode;
   const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
   const bool qwave = plan.scheduler == SCHED_QUEUE_WAVE;
   if (useq && !(blk.qseg && blk.qctr)) {
-    set_error("arrow_spmm: structure has no queue segments");
+    set_error(std::string("arrow_spmm") + Prec<T>::suffix +
+              ": structure has no queue segments");
     return -1;
   }
   int blocks = (int)std::min<int64_t>(
@@ -1144,13 +789,13 @@ int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
     const bool guard = (col_off + span > k);
     auto run = [&](auto kern) {
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         blk.pairs, blk.item_row, blk.item_begin,
+                         a..., blk.item_row, blk.item_begin,
                          blk.item_end, blk.n_items, X0, X1, C, k, col_off,
                          blk.xcd_remap, nt_mode);
     };
     auto runq = [&](auto kern, int chunk) {
       hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         blk.pairs, blk.item_row, blk.item_begin,
+                         a..., blk.item_row, blk.item_begin,
                          blk.item_end, blk.qseg, blk.qctr, chunk,
                          X0, X1, C, k, col_off, nt_mode);
     };
@@ -1158,118 +803,109 @@ int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
       HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
       if (qwave) {
         if (beta == 0) {
-          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 0, true>, plan.chunk_items);
-          else       runq(spmm_kernel_qw<VEC, GROUP, 0, false>, plan.chunk_items);
+          if (guard) runq(spmm_kernel_qw<T, VEC, GROUP, 0, true, A...>, plan.chunk_items);
+          else       runq(spmm_kernel_qw<T, VEC, GROUP, 0, false, A...>, plan.chunk_items);
         } else {
-          if (guard) runq(spmm_kernel_qw<VEC, GROUP, 1, true>, plan.chunk_items);
-          else       runq(spmm_kernel_qw<VEC, GROUP, 1, false>, plan.chunk_items);
+          if (guard) runq(spmm_kernel_qw<T, VEC, GROUP, 1, true, A...>, plan.chunk_items);
+          else       runq(spmm_kernel_qw<T, VEC, GROUP, 1, false, A...>, plan.chunk_items);
         }
       } else if (beta == 0) {
-        if (guard) runq(spmm_kernel_q<VEC, GROUP, 0, true>, plan.chunk_items);
-        else       runq(spmm_kernel_q<VEC, GROUP, 0, false>, plan.chunk_items);
+        if (guard) runq(spmm_kernel_q<T, VEC, GROUP, 0, true, A...>, plan.chunk_items);
+        else       runq(spmm_kernel_q<T, VEC, GROUP, 0, false, A...>, plan.chunk_items);
       } else {
-        if (guard) runq(spmm_kernel_q<VEC, GROUP, 1, true>, plan.chunk_items);
-        else       runq(spmm_kernel_q<VEC, GROUP, 1, false>, plan.chunk_items);
+        if (guard) runq(spmm_kernel_q<T, VEC, GROUP, 1, true, A...>, plan.chunk_items);
+        else       runq(spmm_kernel_q<T, VEC, GROUP, 1, false, A...>, plan.chunk_items);
       }
     } else if (beta == 0) {
-      if (guard) run(spmm_kernel<VEC, GROUP, 0, true>);
-      else       run(spmm_kernel<VEC, GROUP, 0, false>);
+      if (guard) run(spmm_kernel<T, VEC, GROUP, 0, true, A...>);
+      else       run(spmm_kernel<T, VEC, GROUP, 0, false, A...>);
     } else {
-      if (guard) run(spmm_kernel<VEC, GROUP, 1, true>);
-      else       run(spmm_kernel<VEC, GROUP, 1, false>);
+      if (guard) run(spmm_kernel<T, VEC, GROUP, 1, true, A...>);
+      else       run(spmm_kernel<T, VEC, GROUP, 1, false, A...>);
     }
     HIP_CHECK(hipGetLastError());
   }
   return 0;
 }
 
-template <int VEC>
-int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const float *X0,
-                  const float *X1, float *C, int64_t k, int beta,
-                  hipStream_t stream) {
+template <typename T, int VEC, typename... A>
+int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
+                  const T *X1, T *C, int64_t k, int beta, hipStream_t stream,
+                  const A *... a) {
   switch (plan.group) {
-    case 1:  return launch_spmm_vg<VEC, 1>(blk, plan, X0, X1, C, k, beta, stream);
-    case 2:  return launch_spmm_vg<VEC, 2>(blk, plan, X0, X1, C, k, beta, stream);
-    case 4:  return launch_spmm_vg<VEC, 4>(blk, plan, X0, X1, C, k, beta, stream);
-    case 8:  return launch_spmm_vg<VEC, 8>(blk, plan, X0, X1, C, k, beta, stream);
-    case 16: return launch_spmm_vg<VEC, 16>(blk, plan, X0, X1, C, k, beta, stream);
-    case 32: return launch_spmm_vg<VEC, 32>(blk, plan, X0, X1, C, k, beta, stream);
-    default: return launch_spmm_vg<VEC, 64>(blk, plan, X0, X1, C, k, beta, stream);
+    case 1:  return launch_spmm_vg<T, VEC, 1>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 2:  return launch_spmm_vg<T, VEC, 2>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 4:  return launch_spmm_vg<T, VEC, 4>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 8:  return launch_spmm_vg<T, VEC, 8>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 16: return launch_spmm_vg<T, VEC, 16>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 32: return launch_spmm_vg<T, VEC, 32>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    default: return launch_spmm_vg<T, VEC, 64>(blk, plan, X0, X1, C, k, beta, stream, a...);
   }
 }
 
-template <int VEC, int GROUP>
-int launch_spmm_vg_f64(const CsrBlock &blk, const SpmmPlan &plan,
-                       const double *X0, const double *X1, double *C,
-                       int64_t k, int beta, hipStream_t stream) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
-  const int nt_mode = plan.nt_mode;
-  const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
-  const bool qwave = plan.scheduler == SCHED_QUEUE_WAVE;
-  if (useq && !(blk.qseg && blk.qctr)) {
-    set_error("arrow_spmm_f64: structure has no queue segments");
+// arrow_spmm_dual / arrow_spmm_dual_f64. Error texts name the entry point
+// family of T ("arrow_spmm" + suffix) and, for a handle of the other
+// precision, the family it belongs to.
+template <typename T>
+int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
+                   int64_t k, int beta, void *stream_v) {
+  using P = Prec<T>;
+  using Other = Prec<std::conditional_t<P::dtype == 32, double, float>>;
+  const std::string who = std::string("arrow_spmm") + P::suffix;
+  auto it = g_blocks.find(handle);
+  if (it == g_blocks.end()) {
+    set_error(who + ": bad handle");
     return -1;
   }
-  int blocks = (int)std::min<int64_t>(
-      (blk.n_items + GROUPS_PER_BLOCK - 1) / GROUPS_PER_BLOCK, plan.grid_cap);
-  if (blocks < 1) blocks = 1;
-  const int64_t span = (int64_t)GROUP * VEC;
-  for (int64_t col_off = 0; col_off < k; col_off += span) {
-    const bool guard = (col_off + span > k);
-    auto run = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         blk.cols64, blk.vals64, blk.item_row, blk.item_begin,
-                         blk.item_end, blk.n_items, X0, X1, C, k, col_off,
-                         blk.xcd_remap, nt_mode);
-    };
-    auto runq = [&](auto kern, int chunk) {
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         blk.cols64, blk.vals64, blk.item_row, blk.item_begin,
-                         blk.item_end, blk.qseg, blk.qctr, chunk,
-                         X0, X1, C, k, col_off, nt_mode);
-    };
-    if (useq) {
-      HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
-      if (qwave) {
-        if (beta == 0) {
-          if (guard) runq(spmm_kernel_qw_f64<VEC, GROUP, 0, true>, plan.chunk_items);
-          else       runq(spmm_kernel_qw_f64<VEC, GROUP, 0, false>, plan.chunk_items);
-        } else {
-          if (guard) runq(spmm_kernel_qw_f64<VEC, GROUP, 1, true>, plan.chunk_items);
-          else       runq(spmm_kernel_qw_f64<VEC, GROUP, 1, false>, plan.chunk_items);
-        }
-      } else if (beta == 0) {
-        if (guard) runq(spmm_kernel_q_f64<VEC, GROUP, 0, true>, plan.chunk_items);
-        else       runq(spmm_kernel_q_f64<VEC, GROUP, 0, false>, plan.chunk_items);
-      } else {
-        if (guard) runq(spmm_kernel_q_f64<VEC, GROUP, 1, true>, plan.chunk_items);
-        else       runq(spmm_kernel_q_f64<VEC, GROUP, 1, false>, plan.chunk_items);
-      }
-    } else if (beta == 0) {
-      if (guard) run(spmm_kernel_f64<VEC, GROUP, 0, true>);
-      else       run(spmm_kernel_f64<VEC, GROUP, 0, false>);
-    } else {
-      if (guard) run(spmm_kernel_f64<VEC, GROUP, 1, true>);
-      else       run(spmm_kernel_f64<VEC, GROUP, 1, false>);
-    }
+  if (k <= 0 || !X0_dev || !X1_dev || !C_dev) {
+    set_error(who + ": bad arguments");
+    return -1;
+  }
+  const CsrBlock &blk = it->second;
+  if (blk.dtype != P::dtype) {
+    const std::string o = Other::suffix;
+    set_error(who + ": handle holds a float" + std::to_string(Other::dtype) +
+              " structure (arrow_csr_create" + o + ") but was passed to the "
+              "float" + std::to_string(P::dtype) + " entry point; use "
+              "arrow_spmm" + o + " / arrow_spmm_dual" + o);
+    return -2;
+  }
+  hipStream_t stream = (hipStream_t)stream_v;
+
+  // beta=0: split rows are accumulated with atomics, so pre-zero them.
+  if (beta == 0 && blk.n_split_rows > 0) {
+    const int64_t total = blk.n_split_rows * k;
+    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(blocks), dim3(256), 0, stream,
+                       C_dev, blk.split_rows, blk.n_split_rows, k);
     HIP_CHECK(hipGetLastError());
   }
-  return 0;
+
+  const SpmmPlan plan =
+      spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, P::dtype);
+  return P::with_stream(blk, [&](const auto *... a) {
+    if constexpr (P::dtype == 32) {
+      if (plan.vec == 4)
+        return launch_spmm_v<T, 4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+    }
+    if (plan.vec == 2)
+      return launch_spmm_v<T, 2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+    return launch_spmm_v<T, 1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+  });
 }
 
-template <int VEC>
-int launch_spmm_v_f64(const CsrBlock &blk, const SpmmPlan &plan,
-                      const double *X0, const double *X1, double *C, int64_t k,
-                      int beta, hipStream_t stream) {
-  switch (plan.group) {
-    case 1:  return launch_spmm_vg_f64<VEC, 1>(blk, plan, X0, X1, C, k, beta, stream);
-    case 2:  return launch_spmm_vg_f64<VEC, 2>(blk, plan, X0, X1, C, k, beta, stream);
-    case 4:  return launch_spmm_vg_f64<VEC, 4>(blk, plan, X0, X1, C, k, beta, stream);
-    case 8:  return launch_spmm_vg_f64<VEC, 8>(blk, plan, X0, X1, C, k, beta, stream);
-    case 16: return launch_spmm_vg_f64<VEC, 16>(blk, plan, X0, X1, C, k, beta, stream);
-    case 32: return launch_spmm_vg_f64<VEC, 32>(blk, plan, X0, X1, C, k, beta, stream);
-    default: return launch_spmm_vg_f64<VEC, 64>(blk, plan, X0, X1, C, k, beta, stream);
+int spmm_plan_export(const char *who, int dtype, int64_t k, int64_t nnz,
+                     int queue_mode, int32_t *out, int n_out) {
+  if (k <= 0 || nnz < 0 || !out || n_out < 0) {
+    set_error(std::string(who) + ": bad arguments");
+    return -1;
   }
+  const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0, dtype);
+  const int32_t fields[ARROW_PLAN_FIELDS] = {
+      p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
+      p.n_launches};
+  for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
+  return ARROW_PLAN_FIELDS;
 }
 
 }  // namespace
@@ -1349,30 +985,29 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
   // COLUMN window of X, so the ~concurrent hub-row streams share the
   // XCD's L2. Output correctness is order-independent (each non-split row
   // appears once; split rows accumulate atomically either way).
-  if (flags & 1) {
-    const int64_t n_it = (int64_t)item_row.size();
-    std::vector<int64_t> order(n_it);
-    for (int64_t i = 0; i < n_it; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int64_t a, int64_t b) {
-                       const int32_t ca = item_begin[a] < item_end[a]
-                                              ? indices[item_begin[a]]
-                                              : INT32_MAX;
-                       const int32_t cb = item_begin[b] < item_end[b]
-                                              ? indices[item_begin[b]]
-                                              : INT32_MAX;
-                       return ca < cb;
-                     });
-    std::vector<int32_t> r2(n_it), b2(n_it), e2(n_it);
-    for (int64_t i = 0; i < n_it; ++i) {
-      r2[i] = item_row[order[i]];
-      b2[i] = item_begin[order[i]];
-      e2[i] = item_end[order[i]];
+  // Stable-sort the items [lo, hi) by their first column (empty items last).
+  auto sort_items_by_first_col = [&](int64_t lo, int64_t hi) {
+    auto first_col = [&](int64_t i) {
+      return item_begin[(size_t)i] < item_end[(size_t)i]
+                 ? indices[item_begin[(size_t)i]]
+                 : INT32_MAX;
+    };
+    std::vector<int64_t> order((size_t)(hi - lo));
+    for (int64_t i = lo; i < hi; ++i) order[(size_t)(i - lo)] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+      return first_col(a) < first_col(b);
+    });
+    std::vector<int32_t> r2(order.size()), b2(order.size()), e2(order.size());
+    for (size_t i = 0; i < order.size(); ++i) {
+      r2[i] = item_row[(size_t)order[i]];
+      b2[i] = item_begin[(size_t)order[i]];
+      e2[i] = item_end[(size_t)order[i]];
     }
-    item_row.swap(r2);
-    item_begin.swap(b2);
-    item_end.swap(e2);
-  }
+    std::copy(r2.begin(), r2.end(), item_row.begin() + (size_t)lo);
+    std::copy(b2.begin(), b2.end(), item_begin.begin() + (size_t)lo);
+    std::copy(e2.begin(), e2.end(), item_end.begin() + (size_t)lo);
+  };
+  if (flags & 1) sort_items_by_first_col(0, blk.n_items);
 
   // nnz-balanced contiguous item segments for the per-XCD queue scheduler
   // (items are in row order — or column order with flags&1 — so a segment
@@ -1401,32 +1036,7 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
   // inside the segment's row range. Order-independent for correctness
   // (each non-split row appears once; split rows accumulate atomically).
   if (flags & 2) {
-    for (int q = 0; q < 8; ++q) {
-      const int64_t lo = qseg_h[q], hi = qseg_h[q + 1];
-      if (hi - lo < 2) continue;
-      std::vector<int64_t> order((size_t)(hi - lo));
-      for (int64_t i = lo; i < hi; ++i) order[(size_t)(i - lo)] = i;
-      std::stable_sort(order.begin(), order.end(),
-                       [&](int64_t a, int64_t b) {
-                         const int32_t ca = item_begin[(size_t)a] < item_end[(size_t)a]
-                                                ? indices[item_begin[(size_t)a]]
-                                                : INT32_MAX;
-                         const int32_t cb = item_begin[(size_t)b] < item_end[(size_t)b]
-                                                ? indices[item_begin[(size_t)b]]
-                                                : INT32_MAX;
-                         return ca < cb;
-                       });
-      std::vector<int32_t> r2((size_t)(hi - lo)), b2((size_t)(hi - lo)),
-          e2((size_t)(hi - lo));
-      for (int64_t i = 0; i < hi - lo; ++i) {
-        r2[(size_t)i] = item_row[(size_t)order[(size_t)i]];
-        b2[(size_t)i] = item_begin[(size_t)order[(size_t)i]];
-        e2[(size_t)i] = item_end[(size_t)order[(size_t)i]];
-      }
-      std::copy(r2.begin(), r2.end(), item_row.begin() + (size_t)lo);
-      std::copy(b2.begin(), b2.end(), item_begin.begin() + (size_t)lo);
-      std::copy(e2.begin(), e2.end(), item_end.begin() + (size_t)lo);
-    }
+    for (int q = 0; q < 8; ++q) sort_items_by_first_col(qseg_h[q], qseg_h[q + 1]);
   }
 
   // fp32: pack (col, val) into 8-byte pairs for the staged kernel loads.
@@ -1557,53 +1167,7 @@ int arrow_csr_set_qblocks(int64_t handle, int blocks) {
 
 int arrow_spmm_dual(int64_t handle, const float *X0_dev, const float *X1_dev,
                     float *C_dev, int64_t k, int beta, void *stream_v) {
-  auto it = g_blocks.find(handle);
-  if (it == g_blocks.end()) {
-    set_error("arrow_spmm: bad handle");
-    return -1;
-  }
-  if (k <= 0 || !X0_dev || !X1_dev || !C_dev) {
-    set_error("arrow_spmm: bad arguments");
-    return -1;
-  }
-  const CsrBlock &blk = it->second;
-  if (blk.dtype != 32) {
-    set_error("arrow_spmm: handle holds a float64 structure "
-              "(arrow_csr_create_f64) but was passed to the float32 entry "
-              "point; use arrow_spmm_f64 / arrow_spmm_dual_f64");
-    return -2;
-  }
-  hipStream_t stream = (hipStream_t)stream_v;
-
-  // beta=0: split rows are accumulated with atomics, so pre-zero them.
-  if (beta == 0 && blk.n_split_rows > 0) {
-    const int64_t total = blk.n_split_rows * k;
-    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(zero_rows_kernel, dim3(blocks), dim3(256), 0, stream,
-                       C_dev, blk.split_rows, blk.n_split_rows, k);
-    HIP_CHECK(hipGetLastError());
-  }
-
-  const SpmmPlan plan = spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks);
-  switch (plan.vec) {
-    case 4: return launch_spmm_v<4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
-    case 2: return launch_spmm_v<2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
-    default: return launch_spmm_v<1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
-  }
-}
-
-int arrow_spmm_plan(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
-                    int n_out) {
-  if (k <= 0 || nnz < 0 || !out || n_out < 0) {
-    set_error("arrow_spmm_plan: bad arguments");
-    return -1;
-  }
-  const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0);
-  const int32_t fields[ARROW_PLAN_FIELDS] = {
-      p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
-      p.n_launches};
-  for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
-  return ARROW_PLAN_FIELDS;
+  return spmm_dual_impl<float>(handle, X0_dev, X1_dev, C_dev, k, beta, stream_v);
 }
 
 int arrow_spmm(int64_t handle, const float *X_dev, float *C_dev, int64_t k,
@@ -1611,40 +1175,15 @@ int arrow_spmm(int64_t handle, const float *X_dev, float *C_dev, int64_t k,
   return arrow_spmm_dual(handle, X_dev, X_dev, C_dev, k, beta, stream_v);
 }
 
+int arrow_spmm_plan(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                    int n_out) {
+  return spmm_plan_export("arrow_spmm_plan", 32, k, nnz, queue_mode, out, n_out);
+}
+
 int arrow_spmm_dual_f64(int64_t handle, const double *X0_dev,
                         const double *X1_dev, double *C_dev, int64_t k,
                         int beta, void *stream_v) {
-  auto it = g_blocks.find(handle);
-  if (it == g_blocks.end()) {
-    set_error("arrow_spmm_f64: bad handle");
-    return -1;
-  }
-  if (k <= 0 || !X0_dev || !X1_dev || !C_dev) {
-    set_error("arrow_spmm_f64: bad arguments");
-    return -1;
-  }
-  const CsrBlock &blk = it->second;
-  if (blk.dtype != 64) {
-    set_error("arrow_spmm_f64: handle holds a float32 structure "
-              "(arrow_csr_create) but was passed to the float64 entry "
-              "point; use arrow_spmm / arrow_spmm_dual");
-    return -2;
-  }
-  hipStream_t stream = (hipStream_t)stream_v;
-
-  // beta=0: split rows are accumulated with atomics, so pre-zero them.
-  if (beta == 0 && blk.n_split_rows > 0) {
-    const int64_t total = blk.n_split_rows * k;
-    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(zero_rows_kernel_f64, dim3(blocks), dim3(256), 0,
-                       stream, C_dev, blk.split_rows, blk.n_split_rows, k);
-    HIP_CHECK(hipGetLastError());
-  }
-
-  const SpmmPlan plan = spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, 64);
-  if (plan.vec == 2)
-    return launch_spmm_v_f64<2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
-  return launch_spmm_v_f64<1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream);
+  return spmm_dual_impl<double>(handle, X0_dev, X1_dev, C_dev, k, beta, stream_v);
 }
 
 int arrow_spmm_f64(int64_t handle, const double *X_dev, double *C_dev,
@@ -1654,27 +1193,20 @@ int arrow_spmm_f64(int64_t handle, const double *X_dev, double *C_dev,
 
 int arrow_spmm_plan_f64(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
                         int n_out) {
-  if (k <= 0 || nnz < 0 || !out || n_out < 0) {
-    set_error("arrow_spmm_plan_f64: bad arguments");
-    return -1;
-  }
-  const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0, 64);
-  const int32_t fields[ARROW_PLAN_FIELDS] = {
-      p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
-      p.n_launches};
-  for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
-  return ARROW_PLAN_FIELDS;
+  return spmm_plan_export("arrow_spmm_plan_f64", 64, k, nnz, queue_mode, out,
+                          n_out);
 }
 
 // float64 routing: the pure copies move each row as 2k floats through the
 // fp32 kernels (bit-exact, and float4 = two doubles when k is even); the
-// two adding forms do double arithmetic.
+// two adding forms are the same kernels instantiated for double.
 int arrow_permute_rows_f64(double *dst, const double *src,
                            const int64_t *dst_idx, const int64_t *src_idx,
                            int64_t n, int64_t k, void *stream) {
-  return launch_permute(0, reinterpret_cast<float *>(dst),
-                        reinterpret_cast<const float *>(src), dst_idx, src_idx,
-                        n, 2 * k, (hipStream_t)stream);
+  return launch_permute<float, false>(reinterpret_cast<float *>(dst),
+                                      reinterpret_cast<const float *>(src),
+                                      dst_idx, src_idx, n, 2 * k,
+                                      (hipStream_t)stream);
 }
 
 int arrow_permute_add_rows_f64(double *dst, const double *src,
@@ -1684,56 +1216,61 @@ int arrow_permute_add_rows_f64(double *dst, const double *src,
     set_error("arrow_permute_add_rows_f64: src_idx is NULL");
     return -1;
   }
-  return launch_route_add_f64(dst, src, dst_idx, src_idx, n, k,
-                              (hipStream_t)stream);
+  return launch_permute<double, true>(dst, src, dst_idx, src_idx, n, k,
+                                      (hipStream_t)stream);
 }
 
 int arrow_gather_rows_f64(const double *src, double *dst, const int64_t *idx,
                           int64_t n, int64_t k, void *stream) {
-  return launch_route(RouteOp::Gather, reinterpret_cast<float *>(dst),
-                      reinterpret_cast<const float *>(src), idx, n, 2 * k,
-                      (hipStream_t)stream);
+  return launch_route<float, RouteOp::Gather>(
+      reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(src),
+      idx, n, 2 * k, (hipStream_t)stream);
 }
 
 int arrow_scatter_rows_f64(double *dst, const double *src, const int64_t *idx,
                            int64_t n, int64_t k, void *stream) {
-  return launch_route(RouteOp::Scatter, reinterpret_cast<float *>(dst),
-                      reinterpret_cast<const float *>(src), idx, n, 2 * k,
-                      (hipStream_t)stream);
+  return launch_route<float, RouteOp::Scatter>(
+      reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(src),
+      idx, n, 2 * k, (hipStream_t)stream);
 }
 
 int arrow_scatter_add_rows_f64(double *dst, const double *src,
                                const int64_t *idx, int64_t n, int64_t k,
                                void *stream) {
-  return launch_route_add_f64(dst, src, idx, nullptr, n, k,
-                              (hipStream_t)stream);
+  return launch_route<double, RouteOp::ScatterAdd>(dst, src, idx, n, k,
+                                                   (hipStream_t)stream);
 }
 
 int arrow_permute_rows_f32(float *dst, const float *src, const int64_t *dst_idx,
                            const int64_t *src_idx, int64_t n, int64_t k,
                            void *stream) {
-  return launch_permute(0, dst, src, dst_idx, src_idx, n, k, (hipStream_t)stream);
+  return launch_permute<float, false>(dst, src, dst_idx, src_idx, n, k,
+                                      (hipStream_t)stream);
 }
 
 int arrow_permute_add_rows_f32(float *dst, const float *src,
                                const int64_t *dst_idx, const int64_t *src_idx,
                                int64_t n, int64_t k, void *stream) {
-  return launch_permute(1, dst, src, dst_idx, src_idx, n, k, (hipStream_t)stream);
+  return launch_permute<float, true>(dst, src, dst_idx, src_idx, n, k,
+                                     (hipStream_t)stream);
 }
 
 int arrow_gather_rows_f32(const float *src, float *dst, const int64_t *idx,
                           int64_t n, int64_t k, void *stream) {
-  return launch_route(RouteOp::Gather, dst, src, idx, n, k, (hipStream_t)stream);
+  return launch_route<float, RouteOp::Gather>(dst, src, idx, n, k,
+                                              (hipStream_t)stream);
 }
 
 int arrow_scatter_rows_f32(float *dst, const float *src, const int64_t *idx,
                            int64_t n, int64_t k, void *stream) {
-  return launch_route(RouteOp::Scatter, dst, src, idx, n, k, (hipStream_t)stream);
+  return launch_route<float, RouteOp::Scatter>(dst, src, idx, n, k,
+                                               (hipStream_t)stream);
 }
 
 int arrow_scatter_add_rows_f32(float *dst, const float *src, const int64_t *idx,
                                int64_t n, int64_t k, void *stream) {
-  return launch_route(RouteOp::ScatterAdd, dst, src, idx, n, k, (hipStream_t)stream);
+  return launch_route<float, RouteOp::ScatterAdd>(dst, src, idx, n, k,
+                                                  (hipStream_t)stream);
 }
 
 }  // extern "C"

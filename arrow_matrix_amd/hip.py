@@ -162,44 +162,21 @@ class CsrBlockGPU:
         data = np.ascontiguousarray(data, dtype=self.dtype)
         self.shape = (rows, cols)
         self.nnz = int(indices.size)
-        if self._f64:
-            rid = (np.ascontiguousarray(row_ids, dtype=np.int64)
-                   if row_ids is not None else None)
-            self._handle = _check(lib.arrow_csr_create_f64(
-                rows, cols, self.nnz,
-                indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                data.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                (rid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-                 if rid is not None else None), int(col_items)),
-                "arrow_csr_create_f64")
-        elif col_items:
-            rid = (np.ascontiguousarray(row_ids, dtype=np.int64)
-                   if row_ids is not None else None)
-            self._handle = _check(lib.arrow_csr_create_opts(
-                rows, cols, self.nnz,
-                indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                (rid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
-                 if rid is not None else None), int(col_items)),
-                "arrow_csr_create_opts")
-        elif row_ids is not None:
-            row_ids = np.ascontiguousarray(row_ids, dtype=np.int64)
-            self._handle = _check(lib.arrow_csr_create_rows(
-                rows, cols, self.nnz,
-                indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                row_ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))),
-                "arrow_csr_create_rows")
-        else:
-            self._handle = _check(lib.arrow_csr_create(
-                rows, cols, self.nnz,
-                indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                data.ctypes.data_as(ctypes.POINTER(ctypes.c_float))),
-                "arrow_csr_create")
+        rid = (np.ascontiguousarray(row_ids, dtype=np.int64)
+               if row_ids is not None else None)
+        # every create entry point reaches the same C routine; null row_ids
+        # and flags 0 are its defaults
+        create, ctype, what = (
+            (lib.arrow_csr_create_f64, ctypes.c_double, "arrow_csr_create_f64")
+            if self._f64 else
+            (lib.arrow_csr_create_opts, ctypes.c_float, "arrow_csr_create_opts"))
+        self._handle = _check(create(
+            rows, cols, self.nnz,
+            indptr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+            indices.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+            data.ctypes.data_as(ctypes.POINTER(ctype)),
+            (rid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+             if rid is not None else None), int(col_items)), what)
 
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0):
         """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr())."""
