@@ -13,7 +13,7 @@ from typing import Union
 import numpy as np
 import torch
 
-from . import graphio, synth
+from . import graphio, hip, synth
 from .arrow_dec import ArrowDecompositionMPI
 from .comm import default_comm
 from .common import wb_logging
@@ -83,7 +83,10 @@ def bench_spmm(path: Union[str, None],
     for i in range(iterations):
         # fresh features on matrix 0 each iteration (arrow_bench.py:113-116)
         rows = max(eng0.n_owned, 1) * width
-        X_p0 = 2 * rng.random((rows, n_features), dtype=datatype) - 1
+        # bfloat16 features: drawn as float32, rounded once by set_features
+        X_p0 = 2 * rng.random((rows, n_features),
+                              dtype=np.float32 if hip.is_bf16(datatype)
+                              else datatype) - 1
         eng0.set_features(X_p0)
         comm.barrier()
 

@@ -27,7 +27,7 @@ from typing import List, Optional
 import numpy as np
 
 
-from . import graphio, tables
+from . import graphio, hip, tables
 from .arrow_matrix import ArrowMatrix
 from .arrow_slim import ArrowSlimMPI
 from .comm import Comm, default_comm
@@ -92,7 +92,8 @@ class ArrowDecompositionMPI:
         permutation slices as returned by load_decomposition_new (lists with
         one entry per decomposition part). dtype (float32 or float64) is
         passed to every engine: on the GPU the precision is fixed here, at
-        construction."""
+        construction. torch.bfloat16 / 'bfloat16'
+        selects bfloat16 features (device='gpu', one process)."""
         assert not slim or block_diagonal  # reference arrow_dec_mpi.py:131
         comm = comm if comm is not None else default_comm()
         if slim:
@@ -222,7 +223,9 @@ class ArrowDecompositionMPI:
                     import torch as _t
                     free, total = _t.cuda.mem_get_info()
                     k = self._n_feature_columns
-                    itemsize = self.engines[0].np_dtype.itemsize
+                    be0 = self.engines[0].backend
+                    itemsize = getattr(be0, 'feat_itemsize',
+                                       self.engines[0].np_dtype.itemsize)
                     need = [itemsize * k * (2 * eng.n_owned * self.width
                                      + 2 * self.width)
                             for eng in self.engines]
@@ -563,7 +566,8 @@ class ArrowDecompositionMPI:
             # inferring cols from max(indices)+1 as csr_matrix would
             n_rows = indptr.size - 1
             A = sparse.csr_matrix((data, indices, indptr), shape=(n_rows, n_rows))
-            A = A.astype(datatype)
+            # bfloat16 is a FEATURE dtype: A stays float32 under it
+            A = A.astype(np.float32 if hip.is_bf16(datatype) else datatype)
             grid: List[List[Optional[object]]] = [[None] * nb for _ in range(nb)]
             # first block-row tiles for owned columns; diagonal + first
             # block-column for owned rows (slim layout,

@@ -27,6 +27,7 @@ from typing import List, Optional
 import numpy as np
 import torch
 
+from . import hip
 from .arrow_matrix import ArrowMatrix
 from .backends import make_backend
 from .comm import Comm
@@ -48,8 +49,16 @@ class ArrowSlimMPI(ArrowMatrix):
         :param dtype: float32 or float64. On the GPU the precision is fixed
         HERE (the resident structures are uploaded at load time, before
         zero_rhs is called); on the cpu device zero_rhs may still choose it,
-        as in the reference."""
+        as in the reference. torch.bfloat16 / 'bfloat16' (device='gpu', one
+        process) stores the FEATURES in bfloat16: A and np_dtype stay
+        float32, sums are fp32, C is rounded once per launch
+        (DESIGN.md §bfloat16 features)."""
         self.comm = comm if comm is not None else Comm()
+        if hip.is_bf16(dtype) and self.comm.size > 1:
+            raise NotImplementedError(
+                "bfloat16 features are single-process only: at world>1 the "
+                "C_0 reduce and the exchanges would sum in bfloat16 (and "
+                "there is no multi-GPU rig to validate them)")
         self.banded = banded
         self.column_comm = self.comm
         self.tiles_per_side = tiles_per_side if tiles_per_side is not None else self.comm.size
@@ -415,18 +424,31 @@ class ArrowSlimMPI(ArrowMatrix):
     def zero_rhs(self, number_of_rows_per_rank: int, number_of_columns: int,
                  dtype=np.float32) -> None:
         assert number_of_rows_per_rank >= 1 and number_of_columns >= 1
+        bf16 = hip.is_bf16(dtype)
+        if bf16 and self.backend.device != 'cuda':
+            raise NotImplementedError(
+                "bfloat16 features run on device='gpu' only: the cpu device "
+                "is the scipy parity reference, which has no bfloat16")
         if self.backend.device == 'cuda':
             # the reference chooses the dtype at zero_rhs time
             # (arrow_slim_mpi.py:354); here the resident structures were
             # uploaded at load time in the engine's precision, so zero_rhs
             # can only confirm it
-            if np.dtype(dtype) != self.np_dtype:
+            built = self.backend.feat_dtype
+            if bf16 != self.backend.bf16 or \
+                    (not bf16 and np.dtype(dtype) != self.np_dtype):
                 raise TypeError(
-                    f"zero_rhs(dtype={np.dtype(dtype)}) on a GPU engine "
-                    f"built for {self.np_dtype}: the precision of a "
+                    f"zero_rhs(dtype={dtype if bf16 else np.dtype(dtype)}) "
+                    f"on a GPU engine "
+                    f"built for {built}: the precision of a "
                     f"GPU engine is fixed when it is constructed — pass "
                     f"dtype= to ArrowSlimMPI / ArrowMPI / "
                     f"ArrowDecompositionMPI.initialize")
+            if bf16 and number_of_columns % 8:
+                raise ValueError(
+                    f"zero_rhs: bfloat16 features need a feature width that "
+                    f"is a multiple of 8 (a kernel lane moves 8 bf16 = 16 "
+                    f"bytes); got k={number_of_columns}")
         elif np.dtype(dtype) != np.float32:
             # the reference chooses the dtype at zero_rhs time
             # (arrow_slim_mpi.py:354)
@@ -458,7 +480,7 @@ class ArrowSlimMPI(ArrowMatrix):
                       ('C_0', (w_, k_)), ('X_0', (w_, k_))]
             if self.banded:
                 shapes += [('X_halo_lo', (w_, k_)), ('X_halo_hi', (w_, k_))]
-            itemsize = self.np_dtype.itemsize
+            itemsize = self.backend.feat_itemsize
             need = sum(itemsize * sh[0] * sh[1] for name, sh in shapes
                        if getattr(self, name) is None
                        or tuple(getattr(self, name).shape) != sh)
@@ -509,8 +531,10 @@ class ArrowSlimMPI(ArrowMatrix):
         """Stores a reference (no copy) when X already lives on this
         engine's device; otherwise moves it there once."""
         assert X is not None
+        bf16 = getattr(self.backend, 'bf16', False)
         if isinstance(X, torch.Tensor) and (X.device.type == self.backend.device
-                                            or (self.backend.device == 'cuda' and X.is_cuda)):
+                                            or (self.backend.device == 'cuda' and X.is_cuda)) \
+                and not (bf16 and X.dtype != torch.bfloat16):
             self.X_i = X
         else:
             self.X_i = self.backend.asarray(X)
@@ -882,6 +906,8 @@ class ArrowSlimMPI(ArrowMatrix):
             stripe[:self.n_owned * w].copy_(self.C_i[:self.n_owned * w])
         full = self.comm.allgather_cat(stripe)
         out = full[:self.tiles_per_side * w]
+        if out.dtype == torch.bfloat16:
+            out = out.float()   # numpy has no bfloat16; the upcast is exact
         out_np = out.cpu().numpy()
         if C is not None:
             C[:] = out_np

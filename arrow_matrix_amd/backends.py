@@ -26,6 +26,10 @@ class CpuBackend:
     device = 'cpu'
 
     def __init__(self, dtype=np.float32):
+        if hip.is_bf16(dtype):
+            raise NotImplementedError(
+                "bfloat16 features run on device='gpu' only: the cpu device "
+                "is the scipy parity reference, which has no bfloat16")
         self.np_dtype = np.dtype(dtype)
         self.torch_dtype = _TORCH_DTYPE[self.np_dtype]
 
@@ -75,12 +79,20 @@ class GpuBackend:
     device = 'cuda'
 
     def __init__(self, device_index: Optional[int] = None, dtype=np.float32):
-        self.np_dtype = np.dtype(dtype)
+        # bfloat16 FEATURES (X, C and everything routed): the matrix values
+        # and np_dtype stay float32, torch_dtype / feat_dtype say bfloat16,
+        # and feat_itemsize is what the HBM-capacity guards count
+        self.bf16 = hip.is_bf16(dtype)
+        self.np_dtype = np.dtype(np.float32 if self.bf16 else dtype)
         if self.np_dtype not in _TORCH_DTYPE:
             raise NotImplementedError(
                 f"the HIP kernels compute in float32 or float64, not "
                 f"{self.np_dtype}")
-        self.torch_dtype = _TORCH_DTYPE[self.np_dtype]
+        self.torch_dtype = (torch.bfloat16 if self.bf16
+                            else _TORCH_DTYPE[self.np_dtype])
+        # what hip.py dispatches the feature kernels on
+        self.feat_dtype = torch.bfloat16 if self.bf16 else self.np_dtype
+        self.feat_itemsize = 2 if self.bf16 else self.np_dtype.itemsize
         if not torch.cuda.is_available():
             raise hip.ArrowSpmmError(
                 "GPU backend requested but no HIP device is available")
@@ -100,7 +112,9 @@ class GpuBackend:
     def asarray(self, x) -> torch.Tensor:
         if isinstance(x, torch.Tensor):
             return x.to(self.torch_device, dtype=self.torch_dtype)
-        return torch.from_numpy(np.ascontiguousarray(x, dtype=self.np_dtype)).to(self.torch_device)
+        t = torch.from_numpy(np.ascontiguousarray(x, dtype=self.np_dtype)).to(self.torch_device)
+        # bf16 features: one round-to-nearest-even cast of the float32 values
+        return t.to(self.torch_dtype) if self.bf16 else t
 
     def index_tensor(self, idx: np.ndarray) -> torch.Tensor:
         return torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64)).to(self.torch_device)
@@ -110,7 +124,8 @@ class GpuBackend:
 
     def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int):
         assert X.is_contiguous() and C.is_contiguous()
-        block.spmm(X.data_ptr(), C.data_ptr(), C.shape[1], beta, self._stream())
+        block.spmm(X.data_ptr(), C.data_ptr(), C.shape[1], beta, self._stream(),
+                   feat_dtype=self.feat_dtype)
 
     def upload_arrays(self, shape, indptr, indices, data, row_ids=None,
                       col_items=False) -> hip.CsrBlockGPU:
@@ -122,7 +137,8 @@ class GpuBackend:
                   X1: torch.Tensor, C: torch.Tensor, beta: int):
         assert X0.is_contiguous() and X1.is_contiguous() and C.is_contiguous()
         block.spmm_dual(X0.data_ptr(), X1.data_ptr(), C.data_ptr(),
-                        C.shape[1], beta, self._stream())
+                        C.shape[1], beta, self._stream(),
+                        feat_dtype=self.feat_dtype)
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         out = torch.empty((idx.shape[0], src.shape[1]), dtype=self.torch_dtype,
@@ -130,34 +146,34 @@ class GpuBackend:
         if idx.shape[0]:
             hip.gather_rows(src.data_ptr(), out.data_ptr(), idx.data_ptr(),
                             idx.shape[0], src.shape[1], self._stream(),
-                            dtype=self.np_dtype)
+                            dtype=self.feat_dtype)
         return out
 
     def scatter_rows(self, dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor):
         if idx.shape[0]:
             hip.scatter_rows(dst.data_ptr(), src.data_ptr(), idx.data_ptr(),
                              idx.shape[0], dst.shape[1], self._stream(),
-                             dtype=self.np_dtype)
+                             dtype=self.feat_dtype)
 
     def scatter_add_rows(self, dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor):
         if idx.shape[0]:
             hip.scatter_add_rows(dst.data_ptr(), src.data_ptr(), idx.data_ptr(),
                                  idx.shape[0], dst.shape[1], self._stream(),
-                                 dtype=self.np_dtype)
+                                 dtype=self.feat_dtype)
 
     def permute_rows(self, dst, dst_idx, src, src_idx):
         if dst_idx.shape[0]:
             hip.permute_rows(dst.data_ptr(), src.data_ptr(), dst_idx.data_ptr(),
                              src_idx.data_ptr(), dst_idx.shape[0], dst.shape[1],
                              self._stream(),
-                             dtype=self.np_dtype)
+                             dtype=self.feat_dtype)
 
     def permute_add_rows(self, dst, dst_idx, src, src_idx):
         if dst_idx.shape[0]:
             hip.permute_add_rows(dst.data_ptr(), src.data_ptr(),
                                  dst_idx.data_ptr(), src_idx.data_ptr(),
                                  dst_idx.shape[0], dst.shape[1], self._stream(),
-                                 dtype=self.np_dtype)
+                                 dtype=self.feat_dtype)
 
     def synchronize(self):
         torch.cuda.synchronize(self.device_index)
@@ -165,6 +181,8 @@ class GpuBackend:
 
 def make_backend(device: str, dtype=np.float32):
     if device in ('gpu', 'cuda'):
+        if hip.is_bf16(dtype):
+            return GpuBackend(dtype=dtype)
         if np.dtype(dtype) not in _TORCH_DTYPE:
             raise NotImplementedError(
                 "the HIP kernels compute in float32 (the reference benchmark "

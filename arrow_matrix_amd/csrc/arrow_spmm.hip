@@ -5,9 +5,9 @@
 // gathers (arrow_dec_mpi.py:421-437,526-544). See include/arrow_spmm.h for
 // the ABI contract.
 //
-// float32 and float64 share every kernel and the launch path: the code is
-// written once over the element type, and Prec<T> below holds the little
-// that differs. A change to the shared body is checked against the build
+// float32, float64 and bfloat16-feature SpMM share every kernel and the
+// launch path: the code is written once over the element type, and Prec<T>
+// below holds the little that differs. A change to the shared body is checked against the build
 // before it with tools/isa_diff.py (gfx950 assembly, kernel by kernel).
 //
 // Kernel design (CSR x tall-skinny dense, k = 1..128 typical; figures are
@@ -47,7 +47,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1003  // float64 entry points (arrow_*_f64)
+#define ARROW_ABI_VERSION 1004  // bfloat16 features (arrow_*_bf16)
 
 namespace {
 
@@ -83,8 +83,18 @@ struct CsrBlock {
   int32_t *item_begin = nullptr;
   int32_t *item_end = nullptr;
   int64_t n_items = 0;
-  int32_t *split_rows = nullptr;  // device: rows needing pre-zero at beta=0
+  // device: [n_split_rows, then the split rows' output rows in ascending
+  // order]. split_rows points at the rows (pre-zeroed at beta=0 by the fp32
+  // and f64 paths); the bf16 kernels search them for a row's scratch slot.
+  int32_t *split_tab = nullptr;
+  int32_t *split_rows = nullptr;
   int64_t n_split_rows = 0;
+  // bf16 features only: fp32 partial sums of the split rows, n_split_rows x
+  // scratch_k floats, all zero between launches. Allocated on the first
+  // arrow_spmm_bf16 call that needs it and only ever grown (never inside a
+  // launch that may be under stream capture: warm up first).
+  float *bf16_scratch = nullptr;
+  int64_t scratch_k = 0;
   // XCD-contiguous item remap for this structure (uniform banded rows only:
   // on hub-heavy structures it serialises the heavy head onto one XCD)
   int xcd_remap = 0;
@@ -102,8 +112,9 @@ int64_t g_next_handle = 1;
 // SpMM kernel, float and double.  GROUP lanes x VEC elements cover
 // min(k, GROUP*VEC) columns; wider k is handled by a column-offset loop over
 // launches (col_off). A lane covers at most 16 bytes of an X row: float4, or
-// double2 (the same bytes). Accumulation is fma in T; split rows add with
-// the hardware global atomic of T.
+// double2 (the same bytes), or 8 bf16. Accumulation is fma in T (in float
+// for bf16 features); split rows add with the hardware global atomic of T
+// (bf16: of float, into the structure's scratch).
 // The per-item body is shared by the three schedulers below (grid-stride,
 // block-grab and wave-grab per-XCD queue) — spmm_process_item computes one
 // work item end to end.
@@ -119,11 +130,84 @@ int64_t g_next_handle = 1;
 //           16-byte record would waste a third of the A stream), a
 //           coalesced 4-B and a coalesced 8-B load per GROUP nonzeros; the
 //           64-bit value travels as two 32-bit shuffles.
+//   bf16  : T = uint16_t, the raw bits of a bfloat16 FEATURE (X and C). A is
+//           the float stream unchanged and every product and partial sum is
+//           fp32: a lane loads 8 bf16 (16 bytes), widens each by a 16-bit
+//           shift, accumulates 8 floats with fmaf and rounds once, on the
+//           way out (plain cast: round-to-nearest-even, NaN stays NaN).
+//           Split rows add their fp32 partials into the structure's scratch
+//           and spmm_finalise_bf16 rounds them once (a bf16 atomic would
+//           round the running sum at every add).
+// Per precision: Acc is the accumulator, XV<VEC> a lane's VEC stored
+// elements, unpack / pack convert between the two (the identity for float
+// and double), split_add is what a split-row item does with its partials.
 template <typename T> struct Prec;
 
-template <> struct Prec<float> {
-  static constexpr int dtype = 32;
+// 8 bf16 in 16 bytes <-> 8 floats. Element 2i is the low half of word i.
+struct Float8 {
+  float e[8];
+  __device__ __forceinline__ float operator[](int j) const { return e[j]; }
+  __device__ __forceinline__ float &operator[](int j) { return e[j]; }
+};
+
+__device__ __forceinline__ Float8 bf16x8_unpack(const uint4 &w) {
+  Float8 f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f.e[2 * i] = __uint_as_float(w[i] << 16);
+    f.e[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+  return f;
+}
+
+__device__ __forceinline__ uint4 bf16x8_pack(const float *s) {
+  typedef float f32x2 __attribute__((ext_vector_type(2)));
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  uint4 w;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const f32x2 v = {s[2 * i], s[2 * i + 1]};
+    w[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+  }
+  return w;
+}
+
+// unpack / pack / split_add of a precision whose stored element is its
+// accumulator (float, double)
+template <typename T> struct PrecSame {
+  using Acc = T;
+  using Word = T;  // element of XV and of the non-temporal store vector
+  template <int VEC> static constexpr int WORDS = VEC;
+  template <int VEC> using XV = HIP_vector_type<T, VEC>;
+  template <int VEC>
+  __device__ static __forceinline__ const XV<VEC> &unpack(const XV<VEC> &x) {
+    return x;
+  }
+  template <int VEC>
+  __device__ static __forceinline__ XV<VEC> pack(const T *s) {
+    XV<VEC> o;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) o[j] = s[j];
+    return o;
+  }
+  template <int VEC>
+  __device__ static __forceinline__ const XV<VEC> &pack(const XV<VEC> &x) {
+    return x;
+  }
+  // the hardware global atomic of T, straight into C
+  template <int VEC, typename... A>
+  __device__ static __forceinline__ void split_add(T *cr, int32_t, int64_t,
+                                                   int64_t, const T *acc,
+                                                   const A *...) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
+  }
+};
+
+template <> struct Prec<float> : PrecSame<float> {
+  static constexpr int dtype = 32;  // of the structure the entry points take
   static constexpr const char *suffix = "";
+  static constexpr const char *name = "float32";
   using Staged = int2;  // one staged nonzero per lane
   // nontemporal A-stream load (each pair is read once by one wave): the
   // builtin wants a native vector type, HIP's int2 is a class
@@ -153,9 +237,10 @@ template <> struct Prec<float> {
   }
 };
 
-template <> struct Prec<double> {
+template <> struct Prec<double> : PrecSame<double> {
   static constexpr int dtype = 64;
   static constexpr const char *suffix = "_f64";
+  static constexpr const char *name = "float64";
   struct Staged { int32_t c, lo, hi; };
   __device__ static __forceinline__ Staged load(int nt, int32_t idx,
                                                 const int32_t *cols,
@@ -188,6 +273,66 @@ template <> struct Prec<double> {
   }
 };
 
+// bf16 features over the float A stream. The kernels' pointer pack carries,
+// after the pairs, the split-row table and the fp32 scratch, so the float
+// and double kernels keep their parameter lists.
+template <> struct Prec<uint16_t> : Prec<float> {
+  static constexpr const char *suffix = "_bf16";
+  static constexpr const char *name = "bfloat16";
+  using Acc = float;
+  using Word = unsigned;
+  template <int VEC> static constexpr int WORDS = VEC / 2;
+  template <int VEC> using XV = uint4;  // VEC is 8
+  __device__ static __forceinline__ Staged load(int nt, int32_t idx,
+                                                const int2 *pairs,
+                                                const int32_t *,
+                                                const float *) {
+    return Prec<float>::load(nt, idx, pairs);
+  }
+  template <int VEC>
+  __device__ static __forceinline__ Float8 unpack(const uint4 &x) {
+    return bf16x8_unpack(x);
+  }
+  template <int VEC>
+  __device__ static __forceinline__ uint4 pack(const float *s) {
+    return bf16x8_pack(s);
+  }
+  template <int VEC>
+  __device__ static __forceinline__ uint4 pack(const Float8 &x) {
+    return bf16x8_pack(x.e);
+  }
+  // tab[0] = n >= 1 (the structure has a split item), tab[1..n] ascending
+  // and holding `row`: its index is the scratch slot. Clamped, so that even
+  // a row that were missing could not index outside the scratch.
+  __device__ static __forceinline__ int32_t split_slot(int32_t row,
+                                                       const int32_t *tab) {
+    const int32_t n = tab[0];
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+      const int32_t mid = (lo + hi) >> 1;
+      if (tab[1 + mid] < row) lo = mid + 1;
+      else                    hi = mid;
+    }
+    return lo < n ? lo : n - 1;
+  }
+  template <int VEC>
+  __device__ static __forceinline__ void split_add(uint16_t *, int32_t row,
+                                                   int64_t k, int64_t col0,
+                                                   const float *acc,
+                                                   const int2 *,
+                                                   const int32_t *tab,
+                                                   const float *scratch) {
+    float *sr = const_cast<float *>(scratch) +
+                (int64_t)split_slot(row, tab) * k + col0;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) atomicAdd(sr + j, acc[j]);
+  }
+  template <typename F> static int with_stream(const CsrBlock &blk, F f) {
+    return f(blk.pairs, (const int32_t *)blk.split_tab,
+             (const float *)blk.bf16_scratch);
+  }
+};
+
 template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __device__ __forceinline__ void spmm_process_item(
     int32_t row_raw, int32_t b, int32_t e, const T *__restrict__ X0,
@@ -195,17 +340,19 @@ __device__ __forceinline__ void spmm_process_item(
     bool active, int lane_in_group, int nt_mode, const A *__restrict__... a) {
   using P = Prec<T>;
   using Staged = typename P::Staged;
-  using XV = HIP_vector_type<T, VEC>;  // a lane's VEC elements of an X/C row
-  // a lane covers 16 bytes (float4 / double2): the widest load, the batched
-  // consume4 / consume8 and the vector write-back are for this layout only
+  using Acc = typename P::Acc;  // products and partial sums
+  using XV = typename P::template XV<VEC>;  // a lane's VEC elements of a row
+  // a lane covers 16 bytes of storage (float4 / double2 / 8 bf16): the
+  // widest load, the batched consume4 / consume8 and the vector write-back
+  // are for this layout only
   constexpr bool LANE16 = VEC * sizeof(T) == 16;
 
   const int32_t row = row_raw & 0x7fffffff;
   const bool is_split = row_raw < 0;
 
-  T acc[VEC];
+  Acc acc[VEC];
 #pragma unroll
-  for (int j = 0; j < VEC; ++j) acc[j] = T(0);
+  for (int j = 0; j < VEC; ++j) acc[j] = Acc(0);
 
   // Stage GROUP nonzeros cooperatively (ONE coalesced record load per lane
   // per GROUP nonzeros), then broadcast them across the group with wave
@@ -219,13 +366,14 @@ __device__ __forceinline__ void spmm_process_item(
     return P::template val<GROUP>(mine, u);
   };
   // acc += v * x, lane element by lane element
-  auto axpy = [&](T v, const XV &x) {
+  auto axpy = [&](Acc v, const XV &xs) {
+    const auto &x = P::template unpack<VEC>(xs);
 #pragma unroll
     for (int j = 0; j < VEC; ++j) acc[j] = P::mad(v, x[j], acc[j]);
   };
   auto consume = [&](const Staged &mine, int u) {
     const T *xr = xaddr(mine, u);
-    const T v = val(mine, u);
+    const Acc v = val(mine, u);
     if (active) {
       if constexpr (VEC > 1) {
         axpy(v, *reinterpret_cast<const XV *>(xr));
@@ -244,8 +392,8 @@ __device__ __forceinline__ void spmm_process_item(
       const T *p1 = xaddr(mine, u + 1);
       const T *p2 = xaddr(mine, u + 2);
       const T *p3 = xaddr(mine, u + 3);
-      const T v0 = val(mine, u + 0), v1 = val(mine, u + 1);
-      const T v2 = val(mine, u + 2), v3 = val(mine, u + 3);
+      const Acc v0 = val(mine, u + 0), v1 = val(mine, u + 1);
+      const Acc v2 = val(mine, u + 2), v3 = val(mine, u + 3);
       if (active) {
         const XV a0 = *reinterpret_cast<const XV *>(p0);
         const XV a1 = *reinterpret_cast<const XV *>(p1);
@@ -264,7 +412,7 @@ __device__ __forceinline__ void spmm_process_item(
   auto consume8 = [&](const Staged &mine, int u) {
     if constexpr (LANE16 && GROUP >= 8) {
       const T *p[8];
-      T v[8];
+      Acc v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         p[j] = xaddr(mine, u + j);
@@ -311,31 +459,30 @@ __device__ __forceinline__ void spmm_process_item(
   if (active) {
     T *cr = C + (int64_t)row * k + col0;
     if (is_split) {
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) atomicAdd(cr + j, acc[j]);
+      P::template split_add<VEC>(cr, row, k, col0, acc, a...);
     } else if constexpr (BETA == 1) {
       if constexpr (LANE16) {
-        XV old = *reinterpret_cast<XV *>(cr);
+        auto old = P::template unpack<VEC>(*reinterpret_cast<XV *>(cr));
 #pragma unroll
         for (int j = 0; j < VEC; ++j) old[j] += acc[j];
-        *reinterpret_cast<XV *>(cr) = old;
+        *reinterpret_cast<XV *>(cr) = P::template pack<VEC>(old);
       } else {
 #pragma unroll
         for (int j = 0; j < VEC; ++j) cr[j] += acc[j];
       }
     } else {
       if constexpr (LANE16) {
+        const XV packed = P::template pack<VEC>(acc);
         if (nt_mode) {
-          typedef T nt_vec __attribute__((ext_vector_type(VEC)));
+          constexpr int WORDS = P::template WORDS<VEC>;
+          typedef typename P::Word nt_vec
+              __attribute__((ext_vector_type(WORDS)));
           nt_vec outv;
 #pragma unroll
-          for (int j = 0; j < VEC; ++j) outv[j] = acc[j];
+          for (int j = 0; j < WORDS; ++j) outv[j] = packed[j];
           __builtin_nontemporal_store(outv, reinterpret_cast<nt_vec *>(cr));
         } else {
-          XV outv;
-#pragma unroll
-          for (int j = 0; j < VEC; ++j) outv[j] = acc[j];
-          *reinterpret_cast<XV *>(cr) = outv;
+          *reinterpret_cast<XV *>(cr) = packed;
         }
       } else {
 #pragma unroll
@@ -521,6 +668,33 @@ __global__ void zero_rows_kernel(T *__restrict__ C,
   }
 }
 
+// bf16 split rows, after the SpMM launches of one call: round the fp32 sums
+// in the scratch once, C[row] = bf16((BETA ? float(C[row]) : 0) + sum), and
+// leave the scratch zero for the next call. k8 = k / 8; a thread moves one
+// 16-byte piece of C and its 32 bytes of scratch.
+template <int BETA>
+__global__ void spmm_finalise_bf16(uint16_t *__restrict__ C,
+                                   float *__restrict__ scratch,
+                                   const int32_t *__restrict__ rows,
+                                   int64_t n_rows, int64_t k8) {
+  const int64_t total = n_rows * k8;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k8, j = t % k8;
+    float4 *sp = reinterpret_cast<float4 *>(scratch) + 2 * t;
+    const float4 s0 = sp[0], s1 = sp[1];
+    float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    uint4 *cp = reinterpret_cast<uint4 *>(C) + (int64_t)rows[i] * k8 + j;
+    if constexpr (BETA == 1) {
+      const Float8 old = bf16x8_unpack(*cp);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = old[e] + s[e];
+    }
+    *cp = bf16x8_pack(s);
+    sp[0] = sp[1] = float4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Row gather / scatter / scatter-add (permutation routing on-device).
 // ---------------------------------------------------------------------------
@@ -529,14 +703,26 @@ enum class RouteOp { Gather, Scatter, ScatterAdd };
 
 // A lane moves N elements of T: 16 bytes when k allows, else one element.
 // The float64 pure copies run the float kernels on rows of 2k floats, so
-// only the adding forms are instantiated for double.
+// only the adding forms are instantiated for double. bf16 rows (T =
+// uint16_t raw bits, k % 8 == 0) likewise copy as k/2 floats; their adding
+// forms take 8 bf16 of each side, add in fp32 and round once.
 template <typename T, int N>
-using RouteVec = std::conditional_t<N == 1, T, HIP_vector_type<T, N>>;
+using RouteVec = std::conditional_t<
+    N == 1, T,
+    std::conditional_t<sizeof(T) == 2, uint4,
+                       HIP_vector_type<std::conditional_t<sizeof(T) == 2, float, T>, N>>>;
 
 template <typename T, int N>
 __device__ __forceinline__ void route_add(RouteVec<T, N> *d,
                                           const RouteVec<T, N> &v) {
-  if constexpr (N == 1) {
+  if constexpr (sizeof(T) == 2) {
+    static_assert(N == 8, "bf16 rows move 16 bytes per lane");
+    const Float8 a = bf16x8_unpack(*d), b = bf16x8_unpack(v);
+    float sum[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum[j] = a[j] + b[j];
+    *d = bf16x8_pack(sum);
+  } else if constexpr (N == 1) {
     *d += v;
   } else {
     RouteVec<T, N> b = *d;
@@ -605,8 +791,12 @@ int launch_permute(T *dst, const T *src, const int64_t *dst_idx,
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, dst, src,
                        dst_idx, src_idx, n, k_vec);
   };
-  if (vec) launch(permute_rows_kernel<T, N, ADD>);
-  else     launch(permute_rows_kernel<T, 1, ADD>);
+  if constexpr (sizeof(T) == 2) {  // bf16: the caller checked k % 8 == 0
+    launch(permute_rows_kernel<T, N, ADD>);
+  } else {
+    if (vec) launch(permute_rows_kernel<T, N, ADD>);
+    else     launch(permute_rows_kernel<T, 1, ADD>);
+  }
   HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -625,8 +815,12 @@ int launch_route(T *dst, const T *src, const int64_t *idx, int64_t n,
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, dst, src,
                        idx, n, k_vec);
   };
-  if (vec) launch(route_rows_kernel<T, N, OP>);
-  else     launch(route_rows_kernel<T, 1, OP>);
+  if constexpr (sizeof(T) == 2) {  // bf16: the caller checked k % 8 == 0
+    launch(route_rows_kernel<T, N, OP>);
+  } else {
+    if (vec) launch(route_rows_kernel<T, N, OP>);
+    else     launch(route_rows_kernel<T, 1, OP>);
+  }
   HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -717,13 +911,16 @@ struct SpmmPlan {
   int n_launches;   // col_off launches = ceil(k / (group * vec))
 };
 
-// A lane holds VEC elements, 16 bytes when k allows: float4 / double2.
+// A lane holds VEC elements, 16 bytes when k allows: float4 / double2, and
+// always 8 bf16 (dtype 16: the callers refuse k % 8 != 0).
 // ARROW_SPMM_G64 / ARROW_K16_G8 are fp32 layout experiments and do not
-// apply to float64.
+// apply to float64 or to bf16 features.
 void pick_cfg(int64_t k, int dtype, int *vec_out, int *group_out) {
   const SpmmEnv &env = spmm_env();
   int vec;
-  if (dtype == 64) {
+  if (dtype == 16) {
+    vec = 8;
+  } else if (dtype == 64) {
     vec = (k % 2 == 0) ? 2 : 1;
   } else {
     if (env.g64 && k == 128) { *vec_out = 2; *group_out = 64; return; }
@@ -739,9 +936,10 @@ void pick_cfg(int64_t k, int dtype, int *vec_out, int *group_out) {
 
 // queue_mode: the structure's arrow_csr_set_queue mode (-1 follows
 // ARROW_QUEUE); q_blocks_override: its arrow_csr_set_qblocks value (0 = none).
-// dtype 32 or 64 only selects the (vec, group) layout: the scheduler policy
-// and its thresholds are shared (a lane is 16 bytes in both precisions, so
-// GROUP-based thresholds carry over by row bytes; measured for fp32 only).
+// dtype 32, 64 or 16 (bf16 features) only selects the (vec, group) layout:
+// the scheduler policy and its thresholds are shared (a lane is 16 bytes in
+// every precision, so GROUP-based thresholds carry over by row bytes;
+// measured for fp32 only).
 SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
                    int q_blocks_override, int dtype = 32) {
   const SpmmEnv &env = spmm_env();
@@ -846,11 +1044,43 @@ int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
 // arrow_spmm_dual / arrow_spmm_dual_f64. Error texts name the entry point
 // family of T ("arrow_spmm" + suffix) and, for a handle of the other
 // precision, the family it belongs to.
+// bf16 features need k % 8 == 0: a row is then a whole number of 16-byte
+// lanes and 16-byte aligned. The text names the rule.
+bool bf16_k_ok(const std::string &who, int64_t k) {
+  if (k % 8 == 0) return true;
+  set_error(who + ": bfloat16 features need k % 8 == 0 (a lane moves 8 bf16 "
+            "= 16 bytes, rows must be 16-byte aligned); got k = " +
+            std::to_string(k));
+  return false;
+}
+
+// The structure's fp32 scratch for bf16 split rows, n_split_rows x k floats,
+// zero between launches: allocated on first need, grown when a wider k
+// comes, never shrunk. hipMalloc is not legal under stream capture, so the
+// first launch at a given k must come before any capture.
+int ensure_bf16_scratch(CsrBlock &blk, int64_t k, hipStream_t stream) {
+  if (blk.n_split_rows == 0 || blk.scratch_k >= k) return 0;
+  float *p = nullptr;
+  const size_t bytes = (size_t)blk.n_split_rows * (size_t)k * sizeof(float);
+  HIP_CHECK(hipMalloc((void **)&p, bytes));
+  if (blk.bf16_scratch) {
+    // launches that use the old one may still be in flight
+    HIP_CHECK(hipStreamSynchronize(stream));
+    (void)hipFree(blk.bf16_scratch);
+  }
+  blk.bf16_scratch = p;
+  blk.scratch_k = k;
+  HIP_CHECK(hipMemsetAsync(p, 0, bytes, stream));
+  return 0;
+}
+
 template <typename T>
 int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
                    int64_t k, int beta, void *stream_v) {
   using P = Prec<T>;
   using Other = Prec<std::conditional_t<P::dtype == 32, double, float>>;
+  constexpr bool BF16 = std::is_same_v<T, uint16_t>;
+  constexpr int plan_dtype = BF16 ? 16 : P::dtype;
   const std::string who = std::string("arrow_spmm") + P::suffix;
   auto it = g_blocks.find(handle);
   if (it == g_blocks.end()) {
@@ -861,37 +1091,65 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
     set_error(who + ": bad arguments");
     return -1;
   }
-  const CsrBlock &blk = it->second;
+  CsrBlock &blk = it->second;
   if (blk.dtype != P::dtype) {
     const std::string o = Other::suffix;
     set_error(who + ": handle holds a float" + std::to_string(Other::dtype) +
-              " structure (arrow_csr_create" + o + ") but was passed to the "
-              "float" + std::to_string(P::dtype) + " entry point; use "
-              "arrow_spmm" + o + " / arrow_spmm_dual" + o);
+              " structure (arrow_csr_create" + o + ") but was passed to the " +
+              P::name + " entry point" +
+              (BF16 ? ", which takes a float32 structure (arrow_csr_create*)"
+                    : "") +
+              "; use arrow_spmm" + o + " / arrow_spmm_dual" + o);
     return -2;
   }
   hipStream_t stream = (hipStream_t)stream_v;
+  if constexpr (BF16) {
+    if (!bf16_k_ok(who, k)) return -3;
+    if (ensure_bf16_scratch(blk, k, stream)) return -1;
+  }
 
-  // beta=0: split rows are accumulated with atomics, so pre-zero them.
-  if (beta == 0 && blk.n_split_rows > 0) {
-    const int64_t total = blk.n_split_rows * k;
-    int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(blocks), dim3(256), 0, stream,
-                       C_dev, blk.split_rows, blk.n_split_rows, k);
-    HIP_CHECK(hipGetLastError());
+  // beta=0: split rows are accumulated with atomics, so pre-zero them (bf16
+  // split rows go through the scratch and are written whole at the end).
+  if constexpr (!BF16) {
+    if (beta == 0 && blk.n_split_rows > 0) {
+      const int64_t total = blk.n_split_rows * k;
+      int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+      hipLaunchKernelGGL(zero_rows_kernel<T>, dim3(blocks), dim3(256), 0,
+                         stream, C_dev, blk.split_rows, blk.n_split_rows, k);
+      HIP_CHECK(hipGetLastError());
+    }
   }
 
   const SpmmPlan plan =
-      spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, P::dtype);
-  return P::with_stream(blk, [&](const auto *... a) {
-    if constexpr (P::dtype == 32) {
-      if (plan.vec == 4)
-        return launch_spmm_v<T, 4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+      spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, plan_dtype);
+  const int rc = P::with_stream(blk, [&](const auto *... a) {
+    if constexpr (BF16) {
+      return launch_spmm_v<T, 8>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+    } else {
+      if constexpr (P::dtype == 32) {
+        if (plan.vec == 4)
+          return launch_spmm_v<T, 4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+      }
+      if (plan.vec == 2)
+        return launch_spmm_v<T, 2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+      return launch_spmm_v<T, 1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
     }
-    if (plan.vec == 2)
-      return launch_spmm_v<T, 2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
-    return launch_spmm_v<T, 1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
   });
+  if constexpr (BF16) {
+    if (rc == 0 && blk.n_split_rows > 0) {
+      const int64_t total = blk.n_split_rows * (k / 8);
+      int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+      auto fin = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, C_dev,
+                           blk.bf16_scratch, blk.split_rows, blk.n_split_rows,
+                           k / 8);
+      };
+      if (beta == 0) fin(spmm_finalise_bf16<0>);
+      else           fin(spmm_finalise_bf16<1>);
+      HIP_CHECK(hipGetLastError());
+    }
+  }
+  return rc;
 }
 
 int spmm_plan_export(const char *who, int dtype, int64_t k, int64_t nnz,
@@ -900,6 +1158,7 @@ int spmm_plan_export(const char *who, int dtype, int64_t k, int64_t nnz,
     set_error(std::string(who) + ": bad arguments");
     return -1;
   }
+  if (dtype == 16 && !bf16_k_ok(who, k)) return -3;
   const SpmmPlan p = spmm_plan(k, nnz, queue_mode, 0, dtype);
   const int32_t fields[ARROW_PLAN_FIELDS] = {
       p.vec, p.group, p.scheduler, p.nt_mode, p.chunk_items, p.grid_cap,
@@ -978,6 +1237,10 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
   }
   blk.n_items = (int64_t)item_row.size();
   blk.n_split_rows = (int64_t)split_rows.size();
+  // the device table: the count, then the rows ascending (their order does
+  // not matter to the pre-zero pass; the bf16 kernels search them)
+  std::sort(split_rows.begin(), split_rows.end());
+  split_rows.insert(split_rows.begin(), (int32_t)blk.n_split_rows);
 
   // ARROW_CSR_COL_ITEMS: order work items by their first column instead of
   // by row. For hub-heavy structures (the first block-row: long CSR rows
@@ -1065,10 +1328,11 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
       upload((void **)&blk.item_row, item_row.data(), item_row.size() * 4) ||
       upload((void **)&blk.item_begin, item_begin.data(), item_begin.size() * 4) ||
       upload((void **)&blk.item_end, item_end.data(), item_end.size() * 4) ||
-      upload((void **)&blk.split_rows, split_rows.data(), split_rows.size() * 4) ||
+      upload((void **)&blk.split_tab, split_rows.data(), split_rows.size() * 4) ||
       upload((void **)&blk.qseg, qseg_h, sizeof(qseg_h))) {
     return -1;
   }
+  blk.split_rows = blk.split_tab + 1;
   HIP_CHECK(hipMalloc((void **)&blk.qctr, 8 * 32 * sizeof(int32_t)));
   const int64_t h = g_next_handle++;
   g_blocks.emplace(h, blk);
@@ -1105,7 +1369,8 @@ int arrow_csr_destroy(int64_t handle) {
   for (void *p : {(void *)b.pairs, (void *)b.cols64, (void *)b.vals64,
                   (void *)b.item_row,
                   (void *)b.item_begin, (void *)b.item_end,
-                  (void *)b.split_rows, (void *)b.qseg, (void *)b.qctr}) {
+                  (void *)b.split_tab, (void *)b.bf16_scratch,
+                  (void *)b.qseg, (void *)b.qctr}) {
     if (p) (void)hipFree(p);
   }
   g_blocks.erase(it);
@@ -1239,6 +1504,79 @@ int arrow_scatter_add_rows_f64(double *dst, const double *src,
                                void *stream) {
   return launch_route<double, RouteOp::ScatterAdd>(dst, src, idx, n, k,
                                                    (hipStream_t)stream);
+}
+
+// bfloat16 features (ABI 1004): raw bf16 bits over a float32 structure.
+int arrow_spmm_dual_bf16(int64_t handle, const uint16_t *X0_dev,
+                         const uint16_t *X1_dev, uint16_t *C_dev, int64_t k,
+                         int beta, void *stream_v) {
+  return spmm_dual_impl<uint16_t>(handle, X0_dev, X1_dev, C_dev, k, beta,
+                                  stream_v);
+}
+
+int arrow_spmm_bf16(int64_t handle, const uint16_t *X_dev, uint16_t *C_dev,
+                    int64_t k, int beta, void *stream_v) {
+  return arrow_spmm_dual_bf16(handle, X_dev, X_dev, C_dev, k, beta, stream_v);
+}
+
+int arrow_spmm_plan_bf16(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                         int n_out) {
+  return spmm_plan_export("arrow_spmm_plan_bf16", 16, k, nnz, queue_mode, out,
+                          n_out);
+}
+
+// bf16 routing: the pure copies move each row as k/2 floats through the fp32
+// kernels (bit-exact; float4 = 8 bf16); the two adding forms load 16 bytes
+// of each side, add in fp32 and round once.
+#define ARROW_BF16_ROUTE_K(who)                                               \
+  if (!bf16_k_ok(who, k)) return -3
+
+int arrow_permute_rows_bf16(uint16_t *dst, const uint16_t *src,
+                            const int64_t *dst_idx, const int64_t *src_idx,
+                            int64_t n, int64_t k, void *stream) {
+  ARROW_BF16_ROUTE_K("arrow_permute_rows_bf16");
+  return launch_permute<float, false>(reinterpret_cast<float *>(dst),
+                                      reinterpret_cast<const float *>(src),
+                                      dst_idx, src_idx, n, k / 2,
+                                      (hipStream_t)stream);
+}
+
+int arrow_permute_add_rows_bf16(uint16_t *dst, const uint16_t *src,
+                                const int64_t *dst_idx, const int64_t *src_idx,
+                                int64_t n, int64_t k, void *stream) {
+  ARROW_BF16_ROUTE_K("arrow_permute_add_rows_bf16");
+  if (n > 0 && !src_idx) {
+    set_error("arrow_permute_add_rows_bf16: src_idx is NULL");
+    return -1;
+  }
+  return launch_permute<uint16_t, true>(dst, src, dst_idx, src_idx, n, k,
+                                        (hipStream_t)stream);
+}
+
+int arrow_gather_rows_bf16(const uint16_t *src, uint16_t *dst,
+                           const int64_t *idx, int64_t n, int64_t k,
+                           void *stream) {
+  ARROW_BF16_ROUTE_K("arrow_gather_rows_bf16");
+  return launch_route<float, RouteOp::Gather>(
+      reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(src),
+      idx, n, k / 2, (hipStream_t)stream);
+}
+
+int arrow_scatter_rows_bf16(uint16_t *dst, const uint16_t *src,
+                            const int64_t *idx, int64_t n, int64_t k,
+                            void *stream) {
+  ARROW_BF16_ROUTE_K("arrow_scatter_rows_bf16");
+  return launch_route<float, RouteOp::Scatter>(
+      reinterpret_cast<float *>(dst), reinterpret_cast<const float *>(src),
+      idx, n, k / 2, (hipStream_t)stream);
+}
+
+int arrow_scatter_add_rows_bf16(uint16_t *dst, const uint16_t *src,
+                                const int64_t *idx, int64_t n, int64_t k,
+                                void *stream) {
+  ARROW_BF16_ROUTE_K("arrow_scatter_add_rows_bf16");
+  return launch_route<uint16_t, RouteOp::ScatterAdd>(dst, src, idx, n, k,
+                                                     (hipStream_t)stream);
 }
 
 int arrow_permute_rows_f32(float *dst, const float *src, const int64_t *dst_idx,

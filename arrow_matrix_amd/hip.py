@@ -105,6 +105,18 @@ def _load():
         fn = getattr(lib, name + '_f64')
         fn.argtypes = getattr(lib, name + '_f32').argtypes
         fn.restype = ctypes.c_int
+    # bfloat16-feature entry points (ABI 1004); no create call, they take a
+    # float32 structure handle
+    for name in ('arrow_spmm', 'arrow_spmm_dual', 'arrow_spmm_plan'):
+        fn = getattr(lib, name + '_bf16')
+        fn.argtypes = getattr(lib, name).argtypes
+        fn.restype = ctypes.c_int
+    for name in ('arrow_gather_rows', 'arrow_scatter_rows',
+                 'arrow_scatter_add_rows', 'arrow_permute_rows',
+                 'arrow_permute_add_rows'):
+        fn = getattr(lib, name + '_bf16')
+        fn.argtypes = getattr(lib, name + '_f32').argtypes
+        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -119,11 +131,25 @@ def _check(rc, what: str):
     return rc
 
 
+def is_bf16(dtype) -> bool:
+    """True for the two spellings of the bfloat16 feature dtype,
+    torch.bfloat16 and 'bfloat16' (numpy has no bfloat16)."""
+    if isinstance(dtype, str):
+        return dtype == 'bfloat16'
+    return (type(dtype).__module__ == 'torch'
+            and type(dtype).__name__ == 'dtype'
+            and str(dtype) == 'torch.bfloat16')
+
+
 def _suffix(dtype) -> str:
-    """'f32' or 'f64' for a supported dtype; TypeError for any other."""
+    """'f32' or 'f64' for a supported numpy dtype, 'bf16' for torch.bfloat16
+    or 'bfloat16' (features only: A stays float32); TypeError for any
+    other."""
+    if is_bf16(dtype):
+        return 'bf16'
     try:
         dt = np.dtype(dtype)
-    except TypeError:
+    except (TypeError, ValueError):
         dt = None
     if dt == np.float32:
         return 'f32'
@@ -147,7 +173,13 @@ class CsrBlockGPU:
         row order, 1/True global column sort, 2 column sort WITHIN each
         XCD queue segment (two-level). dtype: float32 or float64 — the
         precision of the resident values, fixed here; spmm / spmm_dual
-        then take device pointers of that precision."""
+        then take device pointers of that precision. A float32 structure
+        also serves bfloat16 FEATURES (raw bf16 X and C, fp32 accumulation):
+        pass feat_dtype=torch.bfloat16 / 'bfloat16' to spmm / spmm_dual."""
+        if is_bf16(dtype):
+            raise TypeError("A stays float32 under bfloat16 features: create "
+                            "the structure with dtype=float32 and pass "
+                            "feat_dtype to spmm / spmm_dual")
         self._f64 = _suffix(dtype) == 'f64'
         self.dtype = np.dtype(dtype)
         lib = _load()
@@ -178,10 +210,21 @@ class CsrBlockGPU:
             (rid.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
              if rid is not None else None), int(col_items)), what)
 
-    def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0):
+    def _entry(self, name: str, feat_dtype):
+        """The SpMM entry point for features of feat_dtype (None: the
+        structure's own precision)."""
+        sfx = {'f32': '', 'f64': '_f64', 'bf16': '_bf16'}[
+            _suffix(self.dtype if feat_dtype is None else feat_dtype)]
+        return getattr(_load(), name + sfx), name + sfx
+
+    def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0,
+             feat_dtype=None):
         """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr())."""
         lib = _load()
-        if self._f64:
+        if feat_dtype is not None:
+            fn, name = self._entry('arrow_spmm', feat_dtype)
+            _check(fn(self._handle, X_ptr, C_ptr, k, beta, stream), name)
+        elif self._f64:
             _check(lib.arrow_spmm_f64(self._handle, X_ptr, C_ptr, k, beta,
                                       stream), "arrow_spmm_f64")
         else:
@@ -203,11 +246,15 @@ class CsrBlockGPU:
                "arrow_csr_set_qblocks")
 
     def spmm_dual(self, X0_ptr: int, X1_ptr: int, C_ptr: int, k: int,
-                  beta: int, stream: int = 0):
+                  beta: int, stream: int = 0, feat_dtype=None):
         """Fused dual-operand SpMM: negative column indices (encoded at
         upload as -(idx+1)) read X1 (see include/arrow_spmm.h)."""
         lib = _load()
-        if self._f64:
+        if feat_dtype is not None:
+            fn, name = self._entry('arrow_spmm_dual', feat_dtype)
+            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, k, beta, stream),
+                   name)
+        elif self._f64:
             _check(lib.arrow_spmm_dual_f64(self._handle, X0_ptr, X1_ptr, C_ptr,
                                            k, beta, stream),
                    "arrow_spmm_dual_f64")
@@ -273,12 +320,13 @@ SCHED_GRID_STRIDE, SCHED_QUEUE_BLOCK, SCHED_QUEUE_WAVE = 0, 1, 2
 
 def spmm_plan(k: int, nnz: int, queue_mode: int = -1,
               dtype=np.float32) -> dict:
-    """The launch plan arrow_spmm (or, for dtype float64, arrow_spmm_f64)
-    takes for a structure of `nnz` nonzeros at width k (arrow_spmm_plan /
-    arrow_spmm_plan_f64; needs no device). The ARROW_* kernel-tuning
-    variables are read once per process, on first use."""
-    name = ('arrow_spmm_plan_f64' if _suffix(dtype) == 'f64'
-            else 'arrow_spmm_plan')
+    """The launch plan arrow_spmm (or, for dtype float64, arrow_spmm_f64;
+    for the bfloat16 feature dtype, arrow_spmm_bf16) takes for a structure
+    of `nnz` nonzeros at width k (arrow_spmm_plan / _f64 / _bf16; needs no
+    device). The ARROW_* kernel-tuning variables are read once per process,
+    on first use."""
+    name = {'f32': 'arrow_spmm_plan', 'f64': 'arrow_spmm_plan_f64',
+            'bf16': 'arrow_spmm_plan_bf16'}[_suffix(dtype)]
     out = (ctypes.c_int32 * len(PLAN_FIELDS))()
     n = _check(getattr(_load(), name)(int(k), int(nnz), int(queue_mode), out,
                                       len(PLAN_FIELDS)), name)

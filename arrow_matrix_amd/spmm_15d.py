@@ -55,6 +55,12 @@ class Spmm15D:
         rank = self.comm.rank
         self.x, self.y = rank // c, rank % c  # row-major cartesian coords
 
+        from .hip import is_bf16
+        if is_bf16(dtype):
+            raise NotImplementedError(
+                "the 1.5D baseline is float32/float64: bfloat16 features "
+                "are an arrow-engine option (its reduce would sum in "
+                "bfloat16)")
         self.backend = make_backend(device, dtype)
         A = sparse.csr_matrix(A)
         NI, NK = A.shape

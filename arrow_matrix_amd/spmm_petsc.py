@@ -34,6 +34,12 @@ class SpmmPETSc:
                  device: str = 'cpu', dtype=np.float32):
         self.comm = comm if comm is not None else Comm()
         self.ms = matrix_slice
+        from .hip import is_bf16
+        if is_bf16(dtype):
+            raise NotImplementedError(
+                "SpmmPETSc is the float32/float64 baseline: bfloat16 "
+                "features are an arrow-engine option (its exchange would "
+                "move and sum bfloat16 rows)")
         self.backend = make_backend(device, dtype)
         self.A_local = self.backend.upload_block(matrix_slice.A_i_local)
         self.A_nonlocal = (self.backend.upload_block(matrix_slice.A_i_nonlocal)

@@ -218,6 +218,82 @@ int arrow_permute_add_rows_f64(double *dst_dev, const double *src_dev,
                                const int64_t *src_idx_dev, int64_t n,
                                int64_t k, void *stream);
 
+/* ---------------------------------------------------------------------
+ * bfloat16 features (ABI 1004). Only the STORAGE of the feature matrices X
+ * and C changes: they cross the ABI as uint16_t raw bf16 bits, half the
+ * bytes of the fp32 rows that dominate the traffic. A stays the resident
+ * fp32 (col, val) pairs, every product and every partial sum is fp32
+ * (fmaf), and a C element is rounded to bf16 ONCE per call, by a plain
+ * cast: round-to-nearest-even, NaN stays NaN. The reference has no bf16
+ * mode; these exports stand in for the same cupy `A @ X` CSRMM and host
+ * fancy-indexing as the fp32 ones, for a caller that keeps features in
+ * bf16 and would otherwise upcast.
+ *
+ * There is no create call: the bf16 entry points take a float32 structure
+ * handle (arrow_csr_create, _rows, _opts), so one resident copy of A serves
+ * fp32 and bf16 features alike and arrow_csr_dtype keeps reporting 32. A
+ * float64 handle is refused like any precision mismatch: negative code, a
+ * message naming both, nothing launched.
+ *
+ * k must be a multiple of 8 (a lane moves 8 bf16 = 16 bytes; X and C rows
+ * are then 16-byte aligned, given 16-byte aligned base pointers). Any other
+ * k returns a negative code with a message naming the rule, and launches
+ * nothing. k > 512 is column-tiled over launches.
+ *
+ * Split hub rows (more than 2048 nonzeros) are NOT summed in bf16: their
+ * items add fp32 partials into a per-structure fp32 scratch of
+ * n_split_rows x k floats, and a small finalise kernel writes
+ * C[row] = bf16((beta ? float(C[row]) : 0) + sum) and re-zeroes the
+ * scratch. The scratch is allocated on the first bf16 call that needs it
+ * and grows when a wider k comes (hipMalloc): that first call must not be
+ * under stream capture. RUN ONE WARM-UP CALL AT THE WIDEST k BEFORE ANY
+ * CAPTURE. Two bf16 calls on one structure must not overlap in time.
+ * ------------------------------------------------------------------- */
+
+/* C (+)= A @ X with bf16 X and C (replaces the cupy `A @ X` CSRMM,
+ * arrow_slim_mpi.py:190,211,231). beta = 1 computes
+ * bf16(float(C_old) + A@X). */
+int arrow_spmm_bf16(int64_t handle, const uint16_t *X_dev, uint16_t *C_dev,
+                    int64_t k, int beta, void *stream);
+/* Dual-operand form, as arrow_spmm_dual (arrow_slim_mpi.py:121-144). */
+int arrow_spmm_dual_bf16(int64_t handle, const uint16_t *X0_dev,
+                         const uint16_t *X1_dev, uint16_t *C_dev, int64_t k,
+                         int beta, void *stream);
+
+/* Launch-plan query for the bf16 entry points: the same seven fields as
+ * arrow_spmm_plan, from the same policy and the same once-per-process
+ * environment; needs no device. ARROW_PLAN_VEC reads 8 (bf16 per lane);
+ * GROUP = the power of two >= k / 8, capped at 64. k % 8 != 0 returns a
+ * negative code. The queue policy, wave grabs at GROUP < 8 and the chunk
+ * and grid variables apply unchanged: a lane is still 16 bytes, so the
+ * GROUP-based thresholds carry over by row bytes — but they were MEASURED
+ * FOR FP32 ONLY. ARROW_SPMM_G64 and ARROW_K16_G8 are ignored. */
+int arrow_spmm_plan_bf16(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
+                         int n_out);
+
+/* bf16 routing (replace the host fancy-indexing of arrow_dec_mpi.py for
+ * bf16 rows, k % 8 == 0): gather :421,526; scatter :544; the fused
+ * rank-local permute :526+544 — pure copies, bit-exact. scatter-add :437
+ * and permute-add :421+437 compute bf16(float(dst) + float(src)), one
+ * rounding per element. */
+int arrow_gather_rows_bf16(const uint16_t *src_dev, uint16_t *dst_dev,
+                           const int64_t *idx_dev, int64_t n, int64_t k,
+                           void *stream);
+int arrow_scatter_rows_bf16(uint16_t *dst_dev, const uint16_t *src_dev,
+                            const int64_t *idx_dev, int64_t n, int64_t k,
+                            void *stream);
+int arrow_scatter_add_rows_bf16(uint16_t *dst_dev, const uint16_t *src_dev,
+                                const int64_t *idx_dev, int64_t n, int64_t k,
+                                void *stream);
+int arrow_permute_rows_bf16(uint16_t *dst_dev, const uint16_t *src_dev,
+                            const int64_t *dst_idx_dev,
+                            const int64_t *src_idx_dev, int64_t n, int64_t k,
+                            void *stream);
+int arrow_permute_add_rows_bf16(uint16_t *dst_dev, const uint16_t *src_dev,
+                                const int64_t *dst_idx_dev,
+                                const int64_t *src_idx_dev, int64_t n,
+                                int64_t k, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,175 @@
+"""bfloat16 features through the engine on one GPU:
+load_decomposition_new(datatype=torch.bfloat16) -> initialize(device='gpu',
+dtype=torch.bfloat16) -> zero_rhs(dtype=torch.bfloat16) -> three steps, each
+checked against the float64 product of the engine's own previous output on
+the recomposed matrix, to the derived per-element bound of
+tests/engine_bf16_driver.py. The engine paths that an environment variable
+selects (two-launch layout, L = 2 sequential, full fold, row fold) each run
+in a child process and meet the same bound.
+"""
+import os
+import subprocess
+import sys
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+
+from tests import engine_bf16_driver as drv
+from tests.spmm_cases import SEG_NNZ
+
+pytestmark = pytest.mark.gpu
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DRIVER = os.path.join(REPO, 'tests', 'engine_bf16_driver.py')
+CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
+
+_gpu_stopped = None
+
+
+def _need_gpu():
+    """Every test starts here: after a child has aborted, faulted or hit its
+    limit, no later test of this file starts GPU work, in-process or not."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    if _gpu_stopped:
+        pytest.fail(f"not started: {_gpu_stopped}", pytrace=False)
+
+
+def _within(results, goldens, bounds):
+    assert len(results) == 3
+    for step, (C, G, B) in enumerate(zip(results, goldens, bounds)):
+        err = np.abs(C.astype(np.float64) - G)
+        worst = float((err / np.maximum(B, 1e-300)).max())
+        print(f"step {step}: max err/bound {worst:.3f}, "
+              f"max |G| {float(np.abs(G).max()):.3f}")
+        assert np.isfinite(C).all()
+        assert (err <= B).all(), f"step {step}: max err/bound {worst}"
+        assert np.abs(G).max() > 0
+
+
+@pytest.mark.parametrize("n_blocks,width,k,seed,extra", [
+    ([3], 64, 32, 0, {}),
+    ([4, 2], 50, 8, 1, {}),
+    ([3], 48, 520, 3, {}),
+    # two hub rows of 8000 draws over 2560 columns: about 2450 distinct
+    # nonzeros each, above the 2048 of one work item, so the fused structure
+    # has split rows and the fp32 scratch and its finalise pass run
+    ([5], 512, 8, 5, dict(hub_rows=2, hub_deg=8000)),
+])
+def test_engine_gpu_bf16_steps_within_bound(n_blocks, width, k, seed, extra):
+    _need_gpu()
+    for var in drv.ENGINE_VARS:
+        assert var not in os.environ, var
+    if extra.get('hub_rows'):
+        B0 = drv.make_decomposition(n_blocks, width, seed, **extra)[0][0]
+        assert np.diff(B0.indptr).max() > SEG_NNZ
+    results, goldens, bounds, arrow = drv.run_bf16(
+        n_blocks=n_blocks, width=width, k=k, seed=seed, **extra)
+    be = arrow.B.backend
+    assert be.bf16 and be.np_dtype == np.float32 and be.feat_itemsize == 2
+    assert arrow.B.result_tile().dtype == torch.bfloat16
+    assert arrow.B.feature_tile().dtype == torch.bfloat16
+    _within(results, goldens, bounds)
+
+
+@pytest.mark.parametrize('mode', list(drv.MODES))
+def test_engine_gpu_bf16_paths(mode):
+    """Each environment-selected path, in a child that starts with it."""
+    global _gpu_stopped
+    _need_gpu()
+    variables, kwargs = drv.MODES[mode]
+    env = {k: v for k, v in os.environ.items() if k not in drv.ENGINE_VARS}
+    env.update(variables)
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, 'out.npy')
+        try:
+            p = subprocess.run([sys.executable, DRIVER, mode, out], cwd=REPO,
+                               env=env, capture_output=True, text=True,
+                               timeout=CHILD_LIMIT_S)
+        except subprocess.TimeoutExpired:
+            _gpu_stopped = f"engine child '{mode}' hit its {CHILD_LIMIT_S}s limit"
+            pytest.fail(_gpu_stopped, pytrace=False)
+        if p.returncode < 0 or p.returncode in (134, 139, 124, 137):
+            _gpu_stopped = f"engine child '{mode}' ended with status {p.returncode}"
+            pytest.fail(_gpu_stopped + "\n" + p.stderr[-2000:], pytrace=False)
+        assert p.returncode == 0, p.stderr[-2000:]
+        results, goldens, bounds = np.load(out)
+    assert len(results) == kwargs['iters']
+    _within(results, goldens, bounds)
+
+
+def test_float32_engine_still_meets_its_gate_in_the_same_session():
+    """The float32 engine on the matrix of the first bf16 case, after bf16
+    launches ran in this process: the gate of test_gpu_engine.py."""
+    _need_gpu()
+    results, goldens, _, arrow = drv.run_engine(
+        n_blocks=[3], width=64, k=32, seed=0, dtype=np.float32, iters=1)
+    assert arrow.B.result_tile().dtype == torch.float32
+    np.testing.assert_allclose(results[0], goldens[0], rtol=1e-4, atol=1e-4)
+
+
+def test_zero_rhs_refuses_bad_width_and_other_dtypes():
+    _need_gpu()
+    from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
+    from arrow_matrix_amd.arrow_mpi import ArrowMPI
+    e = ArrowSlimMPI(None, tiles_per_side=2, device='gpu',
+                     dtype=torch.bfloat16)
+    for k in (4, 12, 129):
+        with pytest.raises(ValueError, match='multiple of 8'):
+            e.zero_rhs(8, k, dtype=torch.bfloat16)
+    with pytest.raises(TypeError, match='construct'):
+        e.zero_rhs(8, 8, dtype=np.float32)
+    with pytest.raises(TypeError, match='construct'):
+        e.zero_rhs(8, 8)
+    e.zero_rhs(8, 8, dtype='bfloat16')
+    assert e.C_i.dtype == torch.bfloat16 and e.X_0.dtype == torch.bfloat16
+    e32 = ArrowSlimMPI(None, tiles_per_side=2, device='gpu')
+    with pytest.raises(TypeError, match='construct'):
+        e32.zero_rhs(8, 8, dtype=torch.bfloat16)
+    b = ArrowMPI(None, tiles_per_side=2, device='gpu', dtype=torch.bfloat16)
+    b.zero_rhs(8, 8, dtype=torch.bfloat16)
+    assert b.X_halo_lo.dtype == torch.bfloat16
+
+
+def test_set_features_rounds_numpy_once_and_takes_tensors():
+    _need_gpu()
+    from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
+    from arrow_matrix_amd.backends import make_backend
+    be = make_backend('gpu', torch.bfloat16)
+    assert be.zeros((2, 8)).dtype == torch.bfloat16
+    x = np.array([[257.0, 259.0, 1.0, -0.3]], dtype=np.float32)
+    t = be.asarray(x)
+    assert t.dtype == torch.bfloat16
+    assert t.float().cpu().tolist() == \
+        torch.from_numpy(x).to(torch.bfloat16).float().tolist()
+    assert t.float().cpu()[0, :2].tolist() == [256.0, 260.0]
+    e = ArrowSlimMPI(None, tiles_per_side=2, device='gpu',
+                     dtype='bfloat16')
+    e.zero_rhs(8, 8, dtype='bfloat16')
+    e.set_features(np.ones((16, 8), dtype=np.float32))
+    assert e.X_i.dtype == torch.bfloat16 and e.X_i.is_cuda
+    mine = torch.ones((16, 8), dtype=torch.bfloat16, device='cuda')
+    e.set_features(mine)
+    assert e.X_i is mine                          # no copy
+    e.set_features(torch.ones((16, 8), device='cuda'))   # float32: cast once
+    assert e.X_i.dtype == torch.bfloat16
+
+
+def test_bench_spmm_gpu_bf16():
+    _need_gpu()
+    from arrow_matrix_amd.arrow_bench import bench_spmm
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as td:
+        try:
+            os.chdir(td)
+            arrow = bench_spmm(None, 64, 8, 2, True, 'gpu',
+                               datatype=torch.bfloat16)
+            assert arrow is not None
+            assert arrow.B.result_tile().dtype == torch.bfloat16
+            C = arrow.B.allgather_result()
+            assert C.dtype == np.float32
+            assert np.isfinite(C).all() and np.abs(C).max() > 0
+        finally:
+            os.chdir(cwd)
