@@ -180,7 +180,7 @@ class CsrBlockGPU:
             raise TypeError("A stays float32 under bfloat16 features: create "
                             "the structure with dtype=float32 and pass "
                             "feat_dtype to spmm / spmm_dual")
-        self._f64 = _suffix(dtype) == 'f64'
+        f64 = _suffix(dtype) == 'f64'
         self.dtype = np.dtype(dtype)
         lib = _load()
         if arrays is not None:
@@ -200,7 +200,7 @@ class CsrBlockGPU:
         # and flags 0 are its defaults
         create, ctype, what = (
             (lib.arrow_csr_create_f64, ctypes.c_double, "arrow_csr_create_f64")
-            if self._f64 else
+            if f64 else
             (lib.arrow_csr_create_opts, ctypes.c_float, "arrow_csr_create_opts"))
         self._handle = _check(create(
             rows, cols, self.nnz,
@@ -220,16 +220,8 @@ class CsrBlockGPU:
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0,
              feat_dtype=None):
         """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr())."""
-        lib = _load()
-        if feat_dtype is not None:
-            fn, name = self._entry('arrow_spmm', feat_dtype)
-            _check(fn(self._handle, X_ptr, C_ptr, k, beta, stream), name)
-        elif self._f64:
-            _check(lib.arrow_spmm_f64(self._handle, X_ptr, C_ptr, k, beta,
-                                      stream), "arrow_spmm_f64")
-        else:
-            _check(lib.arrow_spmm(self._handle, X_ptr, C_ptr, k, beta, stream),
-                   "arrow_spmm")
+        fn, name = self._entry('arrow_spmm', feat_dtype)
+        _check(fn(self._handle, X_ptr, C_ptr, k, beta, stream), name)
 
     def set_xcd_remap(self, enable: bool):
         _check(_load().arrow_csr_set_xcd_remap(self._handle, 1 if enable else 0),
@@ -249,18 +241,8 @@ class CsrBlockGPU:
                   beta: int, stream: int = 0, feat_dtype=None):
         """Fused dual-operand SpMM: negative column indices (encoded at
         upload as -(idx+1)) read X1 (see include/arrow_spmm.h)."""
-        lib = _load()
-        if feat_dtype is not None:
-            fn, name = self._entry('arrow_spmm_dual', feat_dtype)
-            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, k, beta, stream),
-                   name)
-        elif self._f64:
-            _check(lib.arrow_spmm_dual_f64(self._handle, X0_ptr, X1_ptr, C_ptr,
-                                           k, beta, stream),
-                   "arrow_spmm_dual_f64")
-        else:
-            _check(lib.arrow_spmm_dual(self._handle, X0_ptr, X1_ptr, C_ptr,
-                                       k, beta, stream), "arrow_spmm_dual")
+        fn, name = self._entry('arrow_spmm_dual', feat_dtype)
+        _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, k, beta, stream), name)
 
     def __del__(self):
         if getattr(self, '_handle', None) is not None and _lib is not None:

@@ -28,8 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-ENGINE_VARS = ('ARROW_FUSE_ALL', 'ARROW_FOLD', 'ARROW_SPLIT_COL',
-               'ARROW_PAR_ROW0', 'ARROW_ROW0_CHUNKS', 'ARROW_REST_CHUNK_NNZ')
+from tests.gpu_children import ENGINE_VARS  # noqa: E402
 
 L1 = dict(n_blocks=[4], width=64, k=16, seed=31, iters=3)
 L2 = dict(n_blocks=[4, 2], width=50, k=8, seed=41, iters=3)

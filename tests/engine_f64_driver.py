@@ -14,8 +14,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-ENGINE_VARS = ('ARROW_FUSE_ALL', 'ARROW_FOLD', 'ARROW_SPLIT_COL',
-               'ARROW_PAR_ROW0', 'ARROW_ROW0_CHUNKS', 'ARROW_REST_CHUNK_NNZ')
+from tests.gpu_children import ENGINE_VARS  # noqa: E402
 
 # mode -> (variables, run_f64 arguments). 'default' is what the parent
 # computes in-process with none of ENGINE_VARS set.

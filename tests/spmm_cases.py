@@ -1,6 +1,7 @@
 """Inputs, references and the environment -> launch-plan table shared by the
 SpMM variant tests (test_plan_policy.py, test_spmm_cases.py on the CPU;
-spmm_variant_driver.py / test_gpu_variants.py on the GPU).
+spmm_driver.py / test_gpu_variants.py on the GPU), and the builders of the
+case tables of every precision (spmm_cases_f64.py, spmm_cases_bf16.py).
 
 Everything is built here, in one place, from fixed seeds and raw CSR arrays.
 This module imports numpy/scipy only: it never touches the GPU.
@@ -261,22 +262,43 @@ def real_bound(case, X0, X1, C0):
 # the environment -> plan table
 # ---------------------------------------------------------------------------
 
+def vec_group_launches(k):
+    """The float32 lookup k -> (vec, group, launches); float64 and bfloat16
+    features have tables of their own and pass theirs as `lookup`."""
+    vec, group = VEC_GROUP[k]
+    return vec, group, -(-k // (vec * group))
+
+
 def plan(k, sched, vec=None, group=None, nt=1, q_mult=4, qw_mult=2,
-         q_blocks=Q_BLOCKS_DEFAULT):
-    """Expected arrow_spmm_plan fields for one launch."""
-    dv, dg = VEC_GROUP[k]
-    vec, group = vec or dv, group or dg
+         q_blocks=Q_BLOCKS_DEFAULT, lookup=vec_group_launches):
+    """Expected arrow_spmm_plan fields for one launch. vec / group: what a
+    layout variable (ARROW_K16_G8, ARROW_SPMM_G64) puts in the table's
+    place."""
+    dv, dg, launches = lookup(k)
+    if vec or group:
+        vec, group = vec or dv, group or dg
+        launches = -(-k // (vec * group))
+    else:
+        vec, group = dv, dg
     chunk = {GRID: 0, QBLOCK: (256 // group) * q_mult,
              QWAVE: (64 // group) * qw_mult}[sched]
     return dict(vec=vec, group=group, scheduler=sched, nt_mode=nt,
                 chunk_items=chunk,
                 grid_cap=GRID_STRIDE_CAP if sched == GRID else q_blocks,
-                launches=-(-k // (vec * group)))
+                launches=launches)
 
 
-def default_queued(k):
+def default_queued(k, lookup=vec_group_launches):
     """set_queue(1), no variables: wave grabs at GROUP < 8, else block grabs."""
-    return QWAVE if VEC_GROUP[k][1] < 8 else QBLOCK
+    return QWAVE if lookup(k)[1] < 8 else QBLOCK
+
+
+def policy(k, nnz, q_min_nnz=32 << 20, lookup=vec_group_launches):
+    """Handle mode -1, ARROW_QUEUE unset: queues need GROUP >= 4 and
+    nnz >= ARROW_Q_MIN_NNZ."""
+    if lookup(k)[1] >= 4 and nnz >= q_min_nnz:
+        return default_queued(k, lookup)
+    return GRID
 
 
 def case(name, k, beta, queue, expect, matrix='std', kind='exact', **opts):
@@ -287,34 +309,39 @@ def case(name, k, beta, queue, expect, matrix='std', kind='exact', **opts):
     return c
 
 
-def _variants(tag, k, sched_of, **pl):
+VARIANTS = ('dual', 'rowids', 'col1', 'col2', 'qb8')
+
+
+def _variants(tag, k, sched_of, plan=plan, variants=VARIANTS, **pl):
     """The std-case variants at one k: dual operand, row_ids scatter,
-    col_items 1 and 2, set_qblocks(8); grid-stride and queued."""
+    col_items 1 and 2, set_qblocks(8); grid-stride and queued. `plan` is the
+    precision's; `variants` names the ones it has."""
     out = []
     for q in (0, 1):
         e = plan(k, sched_of(k) if q else GRID, **pl)
         sfx = f'k{k}_q{q}'
         for beta in (0, 1):
-            out.append(case(f'{tag}_dual_{sfx}_b{beta}', k, beta, q, e,
-                            matrix='std_dual'))
-            out.append(case(f'{tag}_rowids_{sfx}_b{beta}', k, beta, q, e,
-                            row_ids=True))
-        out.append(case(f'{tag}_col1_{sfx}', k, 0, q, e, col_items=1))
-        out.append(case(f'{tag}_col2_{sfx}', k, 1, q, e, col_items=2,
-                        matrix='std_dual'))
-    out.append(case(f'{tag}_qb8_k{k}', k, 0, 1, plan(k, sched_of(k), **pl),
-                    qblocks=8))
-    return out
+            out.append(('dual', case(f'{tag}_dual_{sfx}_b{beta}', k, beta, q,
+                                     e, matrix='std_dual')))
+            out.append(('rowids', case(f'{tag}_rowids_{sfx}_b{beta}', k, beta,
+                                       q, e, row_ids=True)))
+        out.append(('col1', case(f'{tag}_col1_{sfx}', k, 0, q, e,
+                                 col_items=1)))
+        out.append(('col2', case(f'{tag}_col2_{sfx}', k, 1, q, e, col_items=2,
+                                 matrix='std_dual')))
+    out.append(('qb8', case(f'{tag}_qb8_k{k}', k, 0, 1,
+                            plan(k, sched_of(k), **pl), qblocks=8)))
+    return [c for variant, c in out if variant in variants]
 
 
-def _sweep(tag, ks, queue, sched_of, **pl):
+def _sweep(tag, ks, queue, sched_of, plan=plan, **pl):
     return [case(f'{tag}_k{k}_b{beta}', k, beta, queue,
                  plan(k, sched_of(k), **pl))
             for k in ks for beta in (0, 1)]
 
 
-def _real_case(tag, k, queue, expect):
-    return case(f'{tag}_real_k{k}', k, 1, queue, expect, matrix='real',
+def _real_case(tag, k, queue, expect, beta=1):
+    return case(f'{tag}_real_k{k}', k, beta, queue, expect, matrix='real',
                 kind='real')
 
 
@@ -435,7 +462,7 @@ def _env_chunk(tag, **pl):
 
 def _policy(k):
     """Handle mode -1, ARROW_QUEUE unset, nnz >= ARROW_Q_MIN_NNZ."""
-    return default_queued(k) if VEC_GROUP[k][1] >= 4 else GRID
+    return policy(k, nnz=0, q_min_nnz=0)
 
 
 def _env_min_nnz0():
@@ -504,16 +531,19 @@ ROUTE_SHAPES = [(n, k) for n in (0, 1, 500) for k in (1, 3, 4, 33, 128)] \
     + [(33000, 129)]
 
 
-def route_case(op, n, k):
+def route_case(op, n, k, draw=None, seed_prefix=(), add=np.add):
     """Operands and the numpy fancy-indexing reference, bit for bit (a
     single fp32 add per element is the same on both sides). Indices are
-    duplicate-free partial permutations into larger arrays."""
-    rng = np.random.default_rng([ROUTE_OPS.index(op), n, k])
+    duplicate-free partial permutations into larger arrays. The other
+    precisions pass how they draw an operand (default: real_values), the
+    prefix of their RNG seed and how `+=` is computed."""
+    draw = draw or real_values
+    rng = np.random.default_rng([*seed_prefix, ROUTE_OPS.index(op), n, k])
     big = n + 13
     src_rows = n if op in ('scatter', 'scatter_add') else big
     dst_rows = n if op == 'gather' else big
-    src = real_values(rng, (src_rows, k))
-    dst0 = real_values(rng, (dst_rows, k))
+    src = draw(rng, (src_rows, k))
+    dst0 = draw(rng, (dst_rows, k))
     src_idx = rng.permutation(src_rows)[:n].astype(np.int64)
     dst_idx = rng.permutation(dst_rows)[:n].astype(np.int64)
     ref = dst0.copy()
@@ -524,10 +554,10 @@ def route_case(op, n, k):
         ref[dst_idx] = src
         src_idx = None
     elif op == 'scatter_add':
-        ref[dst_idx] += src
+        ref[dst_idx] = add(ref[dst_idx], src)
         src_idx = None
     elif op == 'permute':
         ref[dst_idx] = src[src_idx]
     else:
-        ref[dst_idx] += src[src_idx]
+        ref[dst_idx] = add(ref[dst_idx], src[src_idx])
     return dict(src=src, dst0=dst0, src_idx=src_idx, dst_idx=dst_idx, ref=ref)

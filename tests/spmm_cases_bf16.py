@@ -1,5 +1,5 @@
 """Inputs, references and the expected launch-plan table of the bfloat16-
-feature SpMM tests (test_spmm_cases_bf16.py on the CPU; spmm_bf16_driver.py /
+feature SpMM tests (test_spmm_cases_bf16.py on the CPU; spmm_driver.py /
 test_gpu_bf16_kernels.py on the GPU).
 
 The matrices (`std`, `std_dual`, `real`, `stride`, `zero_rows`), `row_ids`
@@ -39,27 +39,15 @@ K_BAD = (4, 12, 129)            # not a multiple of 8: refused
 K_GPU = (8, 16, 24, 128, 520)
 
 
-def plan(k, sched, nt=1, q_mult=4, qw_mult=2, q_blocks=sc.Q_BLOCKS_DEFAULT):
-    """Expected arrow_spmm_plan_bf16 fields for one launch."""
-    vec, group, launches = PLAN_TABLE[k]
-    chunk = {GRID: 0, QBLOCK: (256 // group) * q_mult,
-             QWAVE: (64 // group) * qw_mult}[sched]
-    return dict(vec=vec, group=group, scheduler=sched, nt_mode=nt,
-                chunk_items=chunk,
-                grid_cap=sc.GRID_STRIDE_CAP if sched == GRID else q_blocks,
-                launches=launches)
+def vec_group_launches(k):
+    return PLAN_TABLE[k]
 
 
-def default_queued(k):
-    """set_queue(1), no variables: wave grabs at GROUP < 8, else block grabs."""
-    return QWAVE if PLAN_TABLE[k][1] < 8 else QBLOCK
-
-
-def policy(k, nnz, q_min_nnz=32 << 20):
-    """Handle mode -1, ARROW_QUEUE unset."""
-    if PLAN_TABLE[k][1] >= 4 and nnz >= q_min_nnz:
-        return default_queued(k)
-    return GRID
+# spmm_cases' plan, default_queued and policy, on this table
+plan = functools.partial(sc.plan, lookup=vec_group_launches)
+default_queued = functools.partial(sc.default_queued,
+                                   lookup=vec_group_launches)
+policy = functools.partial(sc.policy, lookup=vec_group_launches)
 
 
 # ---------------------------------------------------------------------------
@@ -146,33 +134,13 @@ def real_bound(case, X0, X1, C0, G):
 # the environment -> case table
 # ---------------------------------------------------------------------------
 
-def case(name, k, beta, queue, expect, matrix='std', kind='exact', **opts):
-    return sc.case(name, k, beta, queue, expect, matrix=matrix, kind=kind,
-                   **opts)
-
-
-def _sweep(tag, ks, queue, sched_of, **opts):
-    return [case(f'{tag}_k{k}_b{beta}', k, beta, queue,
-                 plan(k, sched_of(k)), **opts)
-            for k in ks for beta in (0, 1)]
-
-
-def _variants(tag, k, sched_of):
-    """std_dual and the row_ids scatter at one k, grid-stride and queued."""
-    out = []
-    for q in (0, 1):
-        e = plan(k, sched_of(k) if q else GRID)
-        for beta in (0, 1):
-            out.append(case(f'{tag}_dual_k{k}_q{q}_b{beta}', k, beta, q, e,
-                            matrix='std_dual'))
-            out.append(case(f'{tag}_rowids_k{k}_q{q}_b{beta}', k, beta, q, e,
-                            row_ids=True))
-    return out
-
-
-def _real_case(tag, k, beta, queue, expect):
-    return case(f'{tag}_real_k{k}', k, beta, queue, expect, matrix='real',
-                kind='real')
+# spmm_cases' builders, with this module's plan; of the std-case variants,
+# std_dual and the row_ids scatter only
+case = sc.case
+VARIANTS = ('dual', 'rowids')
+_sweep = functools.partial(sc._sweep, plan=plan)
+_variants = functools.partial(sc._variants, plan=plan, variants=VARIANTS)
+_real_case = sc._real_case
 
 
 def _env_default():
@@ -192,8 +160,8 @@ def _env_default():
     # 1025 split rows, two column-tiled launches, one finalise over both
     cs.append(case('zero_rows_k1024', 1024, 0, 0, plan(1024, GRID),
                    matrix='zero_rows'))
-    cs.append(_real_case('grid', 128, 0, 0, plan(128, GRID)))
-    cs.append(_real_case('queued', 24, 1, 1, plan(24, QWAVE)))
+    cs.append(_real_case('grid', 128, 0, plan(128, GRID), beta=0))
+    cs.append(_real_case('queued', 24, 1, plan(24, QWAVE)))
     return cs
 
 
@@ -207,11 +175,11 @@ def env_table():
         'qwave1': ({'ARROW_QWAVE': '1'},
                    _sweep('qwave1', K_GPU, 1, wave)
                    + _variants('qwave1', 128, wave)
-                   + [_real_case('qwave1', 128, 1, 1, plan(128, QWAVE))]),
+                   + [_real_case('qwave1', 128, 1, plan(128, QWAVE))]),
         'qwave0': ({'ARROW_QWAVE': '0'},
                    _sweep('qwave0', K_GPU, 1, block)
                    + _variants('qwave0', 16, block)
-                   + [_real_case('qwave0', 8, 1, 1, plan(8, QBLOCK))]),
+                   + [_real_case('qwave0', 8, 1, plan(8, QBLOCK))]),
     }
 
 
@@ -229,27 +197,9 @@ def route_case(op, n, k):
     match fancy indexing bit for bit; the adding forms must equal
     bf16_RNE(float(dst) + float(src)): the fp32 sum of two bf16 values,
     rounded once."""
-    rng = np.random.default_rng([16, sc.ROUTE_OPS.index(op), n, k])
-    big = n + 13
-    src_rows = n if op in ('scatter', 'scatter_add') else big
-    dst_rows = n if op == 'gather' else big
-    src = to_bf16_valued(sc.real_values(rng, (src_rows, k)))
-    dst0 = to_bf16_valued(sc.real_values(rng, (dst_rows, k)))
-    src_idx = rng.permutation(src_rows)[:n].astype(np.int64)
-    dst_idx = rng.permutation(dst_rows)[:n].astype(np.int64)
-    ref = dst0.copy()
-    if op == 'gather':
-        ref[:] = src[src_idx]
-        dst_idx = None
-    elif op == 'scatter':
-        ref[dst_idx] = src
-        src_idx = None
-    elif op == 'scatter_add':
-        ref[dst_idx] = ref[dst_idx] + src          # fp32 add
-        src_idx = None
-    elif op == 'permute':
-        ref[dst_idx] = src[src_idx]
-    else:
-        ref[dst_idx] = ref[dst_idx] + src[src_idx]
-    return dict(src=bf16_bits(src), dst0=bf16_bits(dst0), src_idx=src_idx,
-                dst_idx=dst_idx, ref=bf16_bits(ref))
+    rc = sc.route_case(
+        op, n, k, seed_prefix=[16],
+        draw=lambda rng, shape: to_bf16_valued(sc.real_values(rng, shape)),
+        add=lambda dst, src: to_bf16_valued(dst + src))       # fp32 add
+    return dict(rc, src=bf16_bits(rc['src']), dst0=bf16_bits(rc['dst0']),
+                ref=bf16_bits(rc['ref']))

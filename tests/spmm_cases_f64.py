@@ -1,5 +1,5 @@
 """Inputs, references and the expected launch-plan table of the float64 SpMM
-tests (test_spmm_cases_f64.py on the CPU; spmm_f64_driver.py /
+tests (test_spmm_cases_f64.py on the CPU; spmm_driver.py /
 test_gpu_f64_kernels.py on the GPU).
 
 The matrices (`std`, `std_dual`, `real`, `stride`, `zero_rows`, `remap*`),
@@ -45,29 +45,11 @@ def vec_group_launches(k):
     return PLAN_TABLE[k] if k in PLAN_TABLE else PLAN_EXTRA[k]
 
 
-def plan(k, sched, nt=1, q_mult=4, qw_mult=2, q_blocks=sc.Q_BLOCKS_DEFAULT):
-    """Expected arrow_spmm_plan_f64 fields for one launch; scheduler, chunk
-    and grid cap are derived as spmm_cases.plan derives them."""
-    vec, group, launches = vec_group_launches(k)
-    chunk = {GRID: 0, QBLOCK: (256 // group) * q_mult,
-             QWAVE: (64 // group) * qw_mult}[sched]
-    return dict(vec=vec, group=group, scheduler=sched, nt_mode=nt,
-                chunk_items=chunk,
-                grid_cap=sc.GRID_STRIDE_CAP if sched == GRID else q_blocks,
-                launches=launches)
-
-
-def default_queued(k):
-    """set_queue(1), no variables: wave grabs at GROUP < 8, else block grabs."""
-    return QWAVE if vec_group_launches(k)[1] < 8 else QBLOCK
-
-
-def policy(k, nnz, q_min_nnz=32 << 20):
-    """Handle mode -1, ARROW_QUEUE unset: queues need GROUP >= 4 and
-    nnz >= ARROW_Q_MIN_NNZ."""
-    if vec_group_launches(k)[1] >= 4 and nnz >= q_min_nnz:
-        return default_queued(k)
-    return GRID
+# spmm_cases' plan, default_queued and policy, on this table
+plan = functools.partial(sc.plan, lookup=vec_group_launches)
+default_queued = functools.partial(sc.default_queued,
+                                   lookup=vec_group_launches)
+policy = functools.partial(sc.policy, lookup=vec_group_launches)
 
 
 # ---------------------------------------------------------------------------
@@ -169,39 +151,11 @@ def real_bound(case, X0, X1, C0):
 # the environment -> case table
 # ---------------------------------------------------------------------------
 
-def case(name, k, beta, queue, expect, matrix='std', kind='exact', **opts):
-    return sc.case(name, k, beta, queue, expect, matrix=matrix, kind=kind,
-                   **opts)
-
-
-def _sweep(tag, ks, queue, sched_of, **pl):
-    return [case(f'{tag}_k{k}_b{beta}', k, beta, queue,
-                 plan(k, sched_of(k), **pl))
-            for k in ks for beta in (0, 1)]
-
-
-def _variants(tag, k, sched_of, **pl):
-    """std_dual, row_ids, col_items 1 and 2, set_qblocks(8) at one k."""
-    out = []
-    for q in (0, 1):
-        e = plan(k, sched_of(k) if q else GRID, **pl)
-        sfx = f'k{k}_q{q}'
-        for beta in (0, 1):
-            out.append(case(f'{tag}_dual_{sfx}_b{beta}', k, beta, q, e,
-                            matrix='std_dual'))
-            out.append(case(f'{tag}_rowids_{sfx}_b{beta}', k, beta, q, e,
-                            row_ids=True))
-        out.append(case(f'{tag}_col1_{sfx}', k, 0, q, e, col_items=1))
-        out.append(case(f'{tag}_col2_{sfx}', k, 1, q, e, col_items=2,
-                        matrix='std_dual'))
-    out.append(case(f'{tag}_qb8_k{k}', k, 0, 1, plan(k, sched_of(k), **pl),
-                    qblocks=8))
-    return out
-
-
-def _real_case(tag, k, queue, expect):
-    return case(f'{tag}_real_k{k}', k, 1, queue, expect, matrix='real',
-                kind='real')
+# spmm_cases' builders, with this module's plan
+case = sc.case
+_sweep = functools.partial(sc._sweep, plan=plan)
+_variants = functools.partial(sc._variants, plan=plan)
+_real_case = sc._real_case
 
 
 VARIANT_KS = (8, 64, 130)
@@ -261,26 +215,5 @@ def route_case(op, n, k):
     """spmm_cases.route_case in float64: operands drawn as double, the numpy
     fancy-indexing reference bit for bit (one double add per element is the
     same on both sides)."""
-    rng = np.random.default_rng([64, sc.ROUTE_OPS.index(op), n, k])
-    big = n + 13
-    src_rows = n if op in ('scatter', 'scatter_add') else big
-    dst_rows = n if op == 'gather' else big
-    src = real_values(rng, (src_rows, k))
-    dst0 = real_values(rng, (dst_rows, k))
-    src_idx = rng.permutation(src_rows)[:n].astype(np.int64)
-    dst_idx = rng.permutation(dst_rows)[:n].astype(np.int64)
-    ref = dst0.copy()
-    if op == 'gather':
-        ref[:] = src[src_idx]
-        dst_idx = None
-    elif op == 'scatter':
-        ref[dst_idx] = src
-        src_idx = None
-    elif op == 'scatter_add':
-        ref[dst_idx] += src
-        src_idx = None
-    elif op == 'permute':
-        ref[dst_idx] = src[src_idx]
-    else:
-        ref[dst_idx] += src[src_idx]
-    return dict(src=src, dst0=dst0, src_idx=src_idx, dst_idx=dst_idx, ref=ref)
+    return sc.route_case(op, n, k, draw=real_values, seed_prefix=[64],
+                         add=np.add)

@@ -8,8 +8,6 @@ selects (two-launch layout, L = 2 sequential, full fold, row fold) each run
 in a child process and meet the same bound.
 """
 import os
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
@@ -17,6 +15,7 @@ import pytest
 import torch
 
 from tests import engine_bf16_driver as drv
+from tests import gpu_children
 from tests.spmm_cases import SEG_NNZ
 
 pytestmark = pytest.mark.gpu
@@ -25,16 +24,14 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(REPO, 'tests', 'engine_bf16_driver.py')
 CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
 
-_gpu_stopped = None
-
 
 def _need_gpu():
-    """Every test starts here: after a child has aborted, faulted or hit its
-    limit, no later test of this file starts GPU work, in-process or not."""
+    """Every test starts here: after a child of any test module has
+    aborted, faulted or hit its limit, no later test starts GPU work,
+    in-process or not."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    if _gpu_stopped:
-        pytest.fail(f"not started: {_gpu_stopped}", pytrace=False)
+    gpu_children.fail_if_stopped()
 
 
 def _within(results, goldens, bounds):
@@ -60,7 +57,7 @@ def _within(results, goldens, bounds):
 ])
 def test_engine_gpu_bf16_steps_within_bound(n_blocks, width, k, seed, extra):
     _need_gpu()
-    for var in drv.ENGINE_VARS:
+    for var in gpu_children.ENGINE_VARS:
         assert var not in os.environ, var
     if extra.get('hub_rows'):
         B0 = drv.make_decomposition(n_blocks, width, seed, **extra)[0][0]
@@ -77,24 +74,14 @@ def test_engine_gpu_bf16_steps_within_bound(n_blocks, width, k, seed, extra):
 @pytest.mark.parametrize('mode', list(drv.MODES))
 def test_engine_gpu_bf16_paths(mode):
     """Each environment-selected path, in a child that starts with it."""
-    global _gpu_stopped
     _need_gpu()
     variables, kwargs = drv.MODES[mode]
-    env = {k: v for k, v in os.environ.items() if k not in drv.ENGINE_VARS}
-    env.update(variables)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, 'out.npy')
-        try:
-            p = subprocess.run([sys.executable, DRIVER, mode, out], cwd=REPO,
-                               env=env, capture_output=True, text=True,
-                               timeout=CHILD_LIMIT_S)
-        except subprocess.TimeoutExpired:
-            _gpu_stopped = f"engine child '{mode}' hit its {CHILD_LIMIT_S}s limit"
-            pytest.fail(_gpu_stopped, pytrace=False)
-        if p.returncode < 0 or p.returncode in (134, 139, 124, 137):
-            _gpu_stopped = f"engine child '{mode}' ended with status {p.returncode}"
-            pytest.fail(_gpu_stopped + "\n" + p.stderr[-2000:], pytrace=False)
-        assert p.returncode == 0, p.stderr[-2000:]
+        rc, _, stderr = gpu_children.run_child(
+            [DRIVER, mode, out], variables, gpu_children.ENGINE_VARS,
+            CHILD_LIMIT_S, f"engine child '{mode}'")
+        assert rc == 0, stderr
         results, goldens, bounds = np.load(out)
     assert len(results) == kwargs['iters']
     _within(results, goldens, bounds)

@@ -10,8 +10,6 @@ must match the default path on the same matrix to the same gate; the banded
 decomposition is a matrix of its own, so it is held to its golden.
 """
 import os
-import subprocess
-import sys
 import tempfile
 
 import numpy as np
@@ -19,6 +17,7 @@ import pytest
 import torch
 
 from tests import engine_f64_driver as drv
+from tests import gpu_children
 from tests.spmm_cases import SEG_NNZ
 
 pytestmark = pytest.mark.gpu
@@ -28,16 +27,14 @@ DRIVER = os.path.join(REPO, 'tests', 'engine_f64_driver.py')
 TOL = 1e-12
 CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
 
-_gpu_stopped = None
-
 
 def _need_gpu():
-    """Every test starts here: after a child has aborted, faulted or hit its
-    limit, no later test of this file starts GPU work, in-process or not."""
+    """Every test starts here: after a child of any test module has
+    aborted, faulted or hit its limit, no later test starts GPU work,
+    in-process or not."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    if _gpu_stopped:
-        pytest.fail(f"not started: {_gpu_stopped}", pytrace=False)
+    gpu_children.fail_if_stopped()
 
 
 def _close(C, G):
@@ -81,7 +78,7 @@ _default_cache = {}
 def _default_results(kwargs):
     key = repr(sorted(kwargs.items()))
     if key not in _default_cache:
-        for var in drv.ENGINE_VARS:
+        for var in gpu_children.ENGINE_VARS:
             assert var not in os.environ, var
         _default_cache[key] = drv.run_f64(**kwargs)[0]
     return _default_cache[key]
@@ -90,24 +87,14 @@ def _default_results(kwargs):
 @pytest.mark.parametrize('mode', list(drv.MODES))
 def test_engine_gpu_f64_paths(mode):
     """Each environment-selected path, in a child that starts with it."""
-    global _gpu_stopped
     _need_gpu()
     variables, kwargs = drv.MODES[mode]
-    env = {k: v for k, v in os.environ.items() if k not in drv.ENGINE_VARS}
-    env.update(variables)
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, 'out.npy')
-        try:
-            p = subprocess.run([sys.executable, DRIVER, mode, out], cwd=REPO,
-                               env=env, capture_output=True, text=True,
-                               timeout=CHILD_LIMIT_S)
-        except subprocess.TimeoutExpired:
-            _gpu_stopped = f"engine child '{mode}' hit its {CHILD_LIMIT_S}s limit"
-            pytest.fail(_gpu_stopped, pytrace=False)
-        if p.returncode < 0 or p.returncode in (134, 139, 124, 137):
-            _gpu_stopped = f"engine child '{mode}' ended with status {p.returncode}"
-            pytest.fail(_gpu_stopped + "\n" + p.stderr[-2000:], pytrace=False)
-        assert p.returncode == 0, p.stderr[-2000:]
+        rc, _, stderr = gpu_children.run_child(
+            [DRIVER, mode, out], variables, gpu_children.ENGINE_VARS,
+            CHILD_LIMIT_S, f"engine child '{mode}'")
+        assert rc == 0, stderr
         results, goldens = np.load(out)
     assert results.dtype == np.float64 and len(results) == kwargs['iters']
     for C, G in zip(results, goldens):
