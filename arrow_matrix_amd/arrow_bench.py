@@ -30,7 +30,13 @@ def bench_spmm(path: Union[str, None],
                wandb_api_key: str = None,
                datatype=np.float32,
                slim: bool = True,
-               npy_format: bool = True):
+               npy_format: bool = True,
+               damping: float = None):
+    """damping=D (not in the reference; default off, nothing changes without
+    it) iterates the damped step X <- D * A@X + (1 - D) * X0 instead of
+    drawing fresh features every iteration: X0, the first iteration's
+    features, is the residual of the engine's affine step (PageRank's
+    shape). Single process only."""
     assert width > 0
     assert not slim or blocked  # reference arrow_dec_mpi.py:131
     comm = default_comm()
@@ -84,10 +90,16 @@ def bench_spmm(path: Union[str, None],
         # fresh features on matrix 0 each iteration (arrow_bench.py:113-116)
         rows = max(eng0.n_owned, 1) * width
         # bfloat16 features: drawn as float32, rounded once by set_features
-        X_p0 = 2 * rng.random((rows, n_features),
-                              dtype=np.float32 if hip.is_bf16(datatype)
-                              else datatype) - 1
-        eng0.set_features(X_p0)
+        if damping is None or i == 0:
+            X_p0 = 2 * rng.random((rows, n_features),
+                                  dtype=np.float32 if hip.is_bf16(datatype)
+                                  else datatype) - 1
+            eng0.set_features(X_p0)
+            if damping is not None:
+                arrow.set_affine_step(damping, 1.0 - damping, X_p0)
+        else:
+            # the damped iteration feeds its own result back
+            eng0.set_features(eng0.result_tile())
         comm.barrier()
 
         fail = False

@@ -73,6 +73,8 @@ class ArrowDecompositionMPI:
         # R_i[r] (-1 = unmapped).
         self._folded: Optional[List] = None
         self._fold_maps: Optional[List] = None
+        # affine step (set_affine_step): part 0's (alpha, gamma, R) or None
+        self._affine = None
         self._initialize_all_to_all_tables()
 
     @property
@@ -372,9 +374,58 @@ class ArrowDecompositionMPI:
                 # (row-folded parts keep X/C for the forward exchange)
             eng.zero_rhs(width, n_features, dtype=dtype)
 
+    # -- affine step ---------------------------------------------------------
+
+    def set_affine_step(self, alpha: float = 1.0, gamma: float = 0.0,
+                        residual=None) -> None:
+        """Make every later step() compute X <- alpha * A@X + gamma * R on
+        the whole decomposition (A the recomposed matrix). `residual` is in
+        part 0's layout, like the features given to B.set_features; part 0's
+        engine copies it into a buffer of its own (ArrowSlimMPI.
+        set_affine_step). Call after zero_rhs. Single process only. On the
+        GPU the default single-launch layout and both folds carry the step
+        inside their launches; every other layout runs one tail kernel on
+        part 0's finished result."""
+        if self.comm.size > 1:
+            raise NotImplementedError(
+                "the affine step is single-process only (no multi-GPU rig "
+                "to validate the reduced block row 0 against)")
+        eng0 = self.engines[0]
+        eng0.set_affine_step(alpha, gamma, residual)
+        self._affine = eng0._affine
+
+    def clear_affine_step(self) -> None:
+        self._affine = None
+        self.engines[0].clear_affine_step()
+
+    def _affine_inside(self) -> bool:
+        """True when part 0's own spmm() (and the folded launches) carry the
+        affine step; False when step() runs the plain step and then the
+        tail on part 0's aggregated result."""
+        if self.decomposition_length == 1:
+            return True
+        return (self._folded is not None
+                and self.engines[0].backend.device == 'cuda')
+
     # -- iteration -----------------------------------------------------------
 
     def step(self) -> None:
+        """One iteration; with an affine step set, X <- alpha*A@X + gamma*R
+        (see _step_plain for the plain step)."""
+        if self._affine is None:
+            self._step_plain()
+            return
+        eng0 = self.engines[0]
+        inside = self._affine_inside()
+        eng0._affine = self._affine if inside else None
+        try:
+            self._step_plain()
+        finally:
+            eng0._affine = self._affine
+        if not inside:
+            eng0._affine_tail()
+
+    def _step_plain(self) -> None:
         """One X <- A @ X iteration (reference arrow_dec_mpi.py:283-307).
         At world>1 with L>1 the forward exchange for pair (i, i+1) is
         POSTED asynchronously and part i's SpMM runs while the transfer is
@@ -439,6 +490,9 @@ class ArrowDecompositionMPI:
         each part's X via the forward exchange (band locality kept) and
         folds only the backward cascade into the launch's output rows."""
         eng0 = self.engines[0]
+        # affine step: part 0's launch carried alpha and gamma * R, the
+        # folded beta=1 launches carry alpha only
+        alpha = eng0._affine[0] if eng0._affine is not None else 1.0
         if not self._fold_cols:
             tic = time.perf_counter()
             self._propagate_features()
@@ -451,7 +505,8 @@ class ArrowDecompositionMPI:
                 else self.engines[i].feature_tile()
             if eng0.backend.device == 'cuda':
                 eng0._timed(lambda h=h, X_op=X_op: eng0.backend.spmm_block(
-                    h, X_op, eng0.C_i, 1), h.nnz, h.shape[0], h.x_rows)
+                    h, X_op, eng0.C_i, 1, alpha=alpha),
+                    h.nnz, h.shape[0], h.x_rows)
             else:
                 csr, rid = h
                 eng0.C_i.numpy()[rid] += csr @ X_op.numpy()

@@ -114,6 +114,11 @@ class ArrowSlimMPI(ArrowMatrix):
         # (filled by bench.py for the roofline; list of
         # (start_event, end_event, nnz, c_rows, x_rows) tuples)
         self.kernel_events: Optional[list] = None
+        # affine step X <- alpha*A@X + gamma*R (set_affine_step): None, or
+        # (alpha, gamma, R) with R the engine's own residual buffer (or None
+        # at gamma == 0); never swapped with X / C
+        self._affine = None
+        self._R: Optional[torch.Tensor] = None
 
     # -- data loading --------------------------------------------------------
 
@@ -480,22 +485,18 @@ class ArrowSlimMPI(ArrowMatrix):
                       ('C_0', (w_, k_)), ('X_0', (w_, k_))]
             if self.banded:
                 shapes += [('X_halo_lo', (w_, k_)), ('X_halo_hi', (w_, k_))]
-            itemsize = self.backend.feat_itemsize
-            need = sum(itemsize * sh[0] * sh[1] for name, sh in shapes
-                       if getattr(self, name) is None
-                       or tuple(getattr(self, name).shape) != sh)
-            if need:
-                free, total = _t.cuda.mem_get_info()
-                if need > free:
-                    raise MemoryError(
-                        f"zero_rhs: feature/result buffers need "
-                        f"{need/2**30:.1f} GiB but only {free/2**30:.1f} "
-                        f"GiB of HBM are free (k={k_}, width={w_}, "
-                        f"{self.n_owned} owned blocks). Shard over more "
-                        f"GPUs or reduce k.")
+            if self._R is not None:
+                # the affine step's residual stripe counts like X and C
+                shapes.append(('_R', stripe_sh))
+            self._check_hbm('zero_rhs', shapes, w_, k_)
         self.width = number_of_rows_per_rank
         w, k = number_of_rows_per_rank, number_of_columns
         stripe = (max(self.n_owned, 1) * w, k)
+        if self._R is not None and tuple(self._R.shape) != stripe:
+            raise ValueError(
+                f"zero_rhs: the affine step holds a residual of shape "
+                f"{tuple(self._R.shape)}, the new feature stripe is {stripe}: "
+                f"call clear_affine_step() first and set it again after")
         for name, shape in (('C_i', stripe), ('C_0', (w, k)),
                             ('X_i', stripe), ('X_0', (w, k))):
             buf = getattr(self, name)
@@ -516,6 +517,91 @@ class ArrowSlimMPI(ArrowMatrix):
         # is race-free on the GPU (the reference allocates a fresh C every
         # iteration instead, arrow_slim_mpi.py:125-127)
         self._stripe_bufs = [self.C_i, self.X_i]
+
+    def _check_hbm(self, who, shapes, w_, k_) -> None:
+        """Loud capacity check before allocating (GPU): only buffers of
+        `shapes` ((attribute name, shape) pairs) that would be NEWLY
+        allocated count."""
+        itemsize = self.backend.feat_itemsize
+        need = sum(itemsize * sh[0] * sh[1] for name, sh in shapes
+                   if getattr(self, name) is None
+                   or tuple(getattr(self, name).shape) != sh)
+        if need:
+            free, total = torch.cuda.mem_get_info()
+            if need > free:
+                raise MemoryError(
+                    f"{who}: feature/result buffers need "
+                    f"{need/2**30:.1f} GiB but only {free/2**30:.1f} "
+                    f"GiB of HBM are free (k={k_}, width={w_}, "
+                    f"{self.n_owned} owned blocks). Shard over more "
+                    f"GPUs or reduce k.")
+
+    # -- affine step ---------------------------------------------------------
+
+    def set_affine_step(self, alpha: float = 1.0, gamma: float = 0.0,
+                        residual=None) -> None:
+        """Make every later spmm() compute C = alpha * A@X + gamma * R
+        instead of A@X (PageRank, APPNP, damped diffusion, Chebyshev
+        filters). `residual` has the layout and accepted types of
+        set_features (this rank's stripe; numpy or tensor; a bf16 engine
+        rounds numpy float32 once) and is COPIED into a buffer of the
+        engine's own, allocated here (never inside spmm, so a captured step
+        stays capture-legal) and never swapped with X / C. Call after
+        zero_rhs. Single process only. On the GPU the default single-launch
+        layout carries the step in its write-back (no extra pass); the other
+        layouts run one tail kernel after the plain step (DESIGN.md §affine
+        step)."""
+        if self.comm.size > 1:
+            raise NotImplementedError(
+                "the affine step is single-process only: at world>1 the C_0 "
+                "reduce would have to carry alpha and the residual of block "
+                "row 0 exactly once, and there is no multi-GPU rig to "
+                "validate that")
+        alpha, gamma = float(alpha), float(gamma)
+        if gamma != 0.0 and residual is None:
+            raise ValueError("set_affine_step: gamma != 0 needs a residual")
+        if residual is None:
+            self._affine = (alpha, gamma, None)
+            return
+        if self.C_i is None:
+            raise ValueError("set_affine_step: call zero_rhs first (the "
+                             "residual has the shape of the feature stripe)")
+        shape = tuple(self.C_i.shape)
+        if tuple(residual.shape) != shape:
+            raise ValueError(
+                f"set_affine_step: residual has shape "
+                f"{tuple(residual.shape)}, the feature stripe {shape}")
+        bf16 = getattr(self.backend, 'bf16', False)
+        if isinstance(residual, torch.Tensor):
+            ok = residual.dtype == self.backend.torch_dtype or \
+                (bf16 and residual.dtype == torch.float32)
+        else:
+            ok = np.asarray(residual).dtype == self.np_dtype
+        if not ok:
+            raise TypeError(
+                f"set_affine_step: residual of dtype {residual.dtype} on an "
+                f"engine of {self.backend.torch_dtype}: pass the engine's "
+                f"own dtype (float32 for bfloat16 features, rounded once)")
+        if self.backend.device == 'cuda':
+            self._check_hbm('set_affine_step', [('_R', shape)],
+                            self.width, shape[1])
+        if self._R is None or tuple(self._R.shape) != shape:
+            self._R = self.backend.zeros(shape)
+        self._R.copy_(self.backend.asarray(residual))
+        self._affine = (alpha, gamma, self._R)
+
+    def clear_affine_step(self) -> None:
+        """Back to the plain step X <- A@X; the residual buffer is freed."""
+        self._affine = None
+        self._R = None
+
+    def _affine_tail(self) -> None:
+        """C = alpha * C + gamma * R on this rank's finished result: the
+        layouts whose result no single launch finishes."""
+        alpha, gamma, R = self._affine
+        self.backend.axpby_rows(self.C_i, R, alpha, gamma)
+        # a cached X_0 (the allreduce_x0 fast path) holds the plain C_0
+        self._x0_valid = False
 
     def _select_result_buffer(self):
         if self.X_i is None or self.C_i.data_ptr() != self.X_i.data_ptr():
@@ -620,6 +706,9 @@ class ArrowSlimMPI(ArrowMatrix):
             self.X_0, self.C_0 = self.C_0, self.X_0
             self._x0_valid = True
             self._prev_result = self.C_i
+        if self._affine is not None and not (
+                self.backend.device == 'cuda' and self._A_all is not None):
+            self._affine_tail()
 
     def _timed(self, fn, nnz, c_rows, x_rows):
         """HIP-event instrumentation for the roofline (bench.py)."""
@@ -660,6 +749,13 @@ class ArrowSlimMPI(ArrowMatrix):
             # single process: whole matrix in ONE fused launch, C in place;
             # X_0 == X_i[:w] so the second operand is the stripe itself
             h = self._A_all
+            if self._affine is not None:
+                # the affine step rides in this launch's write-back
+                alpha, gamma, R = self._affine
+                self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i,
+                                                 self.C_i, 0, alpha, gamma, R),
+                            h.nnz, self.n_owned * w, h.x_rows)
+                return
             self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i, self.C_i, 0),
                         h.nnz, self.n_owned * w, h.x_rows)
             return

@@ -48,9 +48,17 @@ class CpuBackend:
         from scipy import sparse
         return sparse.csr_matrix(csr)
 
-    def spmm_block(self, block, X: torch.Tensor, C: torch.Tensor, beta: int):
-        """C (+)= block @ X (scipy kernel, the reference CPU path)."""
+    def spmm_block(self, block, X: torch.Tensor, C: torch.Tensor, beta: int,
+                   alpha: float = 1.0, gamma: float = 0.0, R=None):
+        """C (+)= block @ X (scipy kernel, the reference CPU path); with
+        alpha / gamma / R the affine step C = alpha*(block@X) + gamma*R
+        (+ C), the parity reference of the fused GPU launch."""
         res = block @ X.numpy()
+        if alpha != 1.0 or gamma != 0.0 or R is not None:
+            dt = self.np_dtype.type
+            res = dt(alpha) * res
+            if R is not None:
+                res = res + dt(gamma) * R.numpy()
         if beta == 0:
             C.numpy()[:] = res
         else:
@@ -70,6 +78,14 @@ class CpuBackend:
 
     def permute_add_rows(self, dst, dst_idx, src, src_idx):
         dst[dst_idx] += src[src_idx]
+
+    def axpby_rows(self, C: torch.Tensor, R, alpha: float, gamma: float):
+        """C = alpha * C + gamma * R in place (numpy)."""
+        dt = self.np_dtype.type
+        c = C.numpy()
+        c *= dt(alpha)
+        if R is not None:
+            c += dt(gamma) * R.numpy()
 
     def synchronize(self):
         pass
@@ -122,10 +138,23 @@ class GpuBackend:
     def upload_block(self, csr):
         return hip.CsrBlockGPU(csr, dtype=self.np_dtype)
 
-    def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int):
+    @staticmethod
+    def _affine_kw(alpha, gamma, R, C):
+        """Keywords for the affine entry points, none for the plain step."""
+        if alpha == 1.0 and gamma == 0.0 and R is None:
+            return {}
+        if R is not None:
+            assert R.is_contiguous() and R.shape == C.shape \
+                and R.dtype == C.dtype
+        return dict(alpha=alpha, gamma=gamma,
+                    R_ptr=R.data_ptr() if R is not None else 0)
+
+    def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int,
+                   alpha: float = 1.0, gamma: float = 0.0, R=None):
         assert X.is_contiguous() and C.is_contiguous()
         block.spmm(X.data_ptr(), C.data_ptr(), C.shape[1], beta, self._stream(),
-                   feat_dtype=self.feat_dtype)
+                   feat_dtype=self.feat_dtype,
+                   **self._affine_kw(alpha, gamma, R, C))
 
     def upload_arrays(self, shape, indptr, indices, data, row_ids=None,
                       col_items=False) -> hip.CsrBlockGPU:
@@ -134,11 +163,22 @@ class GpuBackend:
                                dtype=self.np_dtype)
 
     def spmm_dual(self, block: hip.CsrBlockGPU, X0: torch.Tensor,
-                  X1: torch.Tensor, C: torch.Tensor, beta: int):
+                  X1: torch.Tensor, C: torch.Tensor, beta: int,
+                  alpha: float = 1.0, gamma: float = 0.0, R=None):
         assert X0.is_contiguous() and X1.is_contiguous() and C.is_contiguous()
         block.spmm_dual(X0.data_ptr(), X1.data_ptr(), C.data_ptr(),
                         C.shape[1], beta, self._stream(),
-                        feat_dtype=self.feat_dtype)
+                        feat_dtype=self.feat_dtype,
+                        **self._affine_kw(alpha, gamma, R, C))
+
+    def axpby_rows(self, C: torch.Tensor, R, alpha: float, gamma: float):
+        """C = alpha * C + gamma * R in place (arrow_axpby_rows_*)."""
+        assert C.is_contiguous() and (R is None or (
+            R.is_contiguous() and R.shape == C.shape and R.dtype == C.dtype))
+        if C.shape[0]:
+            hip.axpby_rows(C.data_ptr(), R.data_ptr() if R is not None else 0,
+                           C.shape[0], C.shape[1], alpha, gamma,
+                           self._stream(), dtype=self.feat_dtype)
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         out = torch.empty((idx.shape[0], src.shape[1]), dtype=self.torch_dtype,

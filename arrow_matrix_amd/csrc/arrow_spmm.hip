@@ -47,7 +47,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1004  // bfloat16 features (arrow_*_bf16)
+#define ARROW_ABI_VERSION 1005  // affine step (arrow_spmm*_affine*, arrow_axpby_rows_*)
 
 namespace {
 
@@ -333,11 +333,27 @@ template <> struct Prec<uint16_t> : Prec<float> {
   }
 };
 
-template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+// What an item does with its finished sums on the way out, chosen at compile
+// time (EP). NoEpilogue is the plain C (+)= A@X and carries nothing: the
+// plain kernels are the instructions they were before the epilogue existed
+// (profiles/isa_affine_parent_vs_branch.txt). AffineEpilogue is the fused
+// affine step C = alpha * (A@X) + gamma * R (+ C): alpha and gamma are
+// applied in the accumulator type, R is indexed like C (by output row) and
+// is null when gamma == 0, in which case it is never dereferenced.
+struct NoEpilogue {};
+template <typename T> struct AffineEpilogue {
+  const T *R;
+  typename Prec<T>::Acc alpha, gamma;
+};
+
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename EP,
+          typename... A>
 __device__ __forceinline__ void spmm_process_item(
     int32_t row_raw, int32_t b, int32_t e, const T *__restrict__ X0,
     const T *__restrict__ X1, T *__restrict__ C, int64_t k, int64_t col0,
-    bool active, int lane_in_group, int nt_mode, const A *__restrict__... a) {
+    bool active, int lane_in_group, int nt_mode, EP ep,
+    const A *__restrict__... a) {
+  constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
   using P = Prec<T>;
   using Staged = typename P::Staged;
   using Acc = typename P::Acc;  // products and partial sums
@@ -459,7 +475,57 @@ __device__ __forceinline__ void spmm_process_item(
   if (active) {
     T *cr = C + (int64_t)row * k + col0;
     if (is_split) {
+      // affine: the pre-launch pass put gamma * R (+ C) into the row and the
+      // items add alpha * partial. bf16 partials go to the scratch unscaled;
+      // spmm_finalise_affine_bf16 applies alpha and gamma * R once.
+      if constexpr (AFFINE && sizeof(T) != 2) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) acc[j] *= ep.alpha;
+      }
       P::template split_add<VEC>(cr, row, k, col0, acc, a...);
+    } else if constexpr (AFFINE) {
+      // alpha * acc + gamma * r (+ old), one store. The lane that owns 16
+      // bytes of C[row] loads the same 16 bytes of R[row] (cached: R is
+      // reused every step); `active` guards both alike.
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) acc[j] *= ep.alpha;
+      if constexpr (LANE16) {
+        if (ep.R) {
+          const XV rv =
+              *reinterpret_cast<const XV *>(ep.R + (int64_t)row * k + col0);
+          const auto &r = P::template unpack<VEC>(rv);
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] = P::mad(ep.gamma, r[j], acc[j]);
+        }
+        if constexpr (BETA == 1) {
+          const auto &old = P::template unpack<VEC>(*reinterpret_cast<XV *>(cr));
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) acc[j] += old[j];
+          *reinterpret_cast<XV *>(cr) = P::template pack<VEC>(acc);
+        } else {
+          const XV packed = P::template pack<VEC>(acc);
+          if (nt_mode) {
+            constexpr int WORDS = P::template WORDS<VEC>;
+            typedef typename P::Word nt_vec
+                __attribute__((ext_vector_type(WORDS)));
+            nt_vec outv;
+#pragma unroll
+            for (int j = 0; j < WORDS; ++j) outv[j] = packed[j];
+            __builtin_nontemporal_store(outv, reinterpret_cast<nt_vec *>(cr));
+          } else {
+            *reinterpret_cast<XV *>(cr) = packed;
+          }
+        }
+      } else {
+        const T *rr = ep.R ? ep.R + (int64_t)row * k + col0 : nullptr;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+          Acc o = acc[j];
+          if (rr) o = P::mad(ep.gamma, rr[j], o);
+          if constexpr (BETA == 1) o += cr[j];
+          cr[j] = o;
+        }
+      }
     } else if constexpr (BETA == 1) {
       if constexpr (LANE16) {
         auto old = P::template unpack<VEC>(*reinterpret_cast<XV *>(cr));
@@ -497,12 +563,13 @@ __device__ __forceinline__ void spmm_process_item(
 // Software prefetch of the NEXT item's metadata: without it every ~8-nnz
 // item pays a 3-deep dependent load chain (meta -> A stream -> X row) that
 // dominates short power-law rows.
-template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename EP,
+          typename... A>
 __device__ __forceinline__ void spmm_process_items(
     int64_t item, int64_t end, int64_t step, const int32_t *item_row,
     const int32_t *item_begin, const int32_t *item_end, const T *X0,
     const T *X1, T *C, int64_t k, int64_t col0, bool active,
-    int lane_in_group, int nt_mode, const A *... a) {
+    int lane_in_group, int nt_mode, EP ep, const A *... a) {
   int32_t next_row = 0, next_b = 0, next_e = 0;
   if (item < end) {
     next_row = __builtin_nontemporal_load(&item_row[item]);
@@ -519,11 +586,44 @@ __device__ __forceinline__ void spmm_process_items(
       next_b = __builtin_nontemporal_load(&item_begin[nxt]);
       next_e = __builtin_nontemporal_load(&item_end[nxt]);
     }
-    spmm_process_item<T, VEC, GROUP, BETA, GUARD>(
-        row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group, nt_mode,
+    spmm_process_item<T, VEC, GROUP, BETA, GUARD, EP>(
+        row_raw, b, e, X0, X1, C, k, col0, active, lane_in_group, nt_mode, ep,
         a...);
   }
 }
+
+// Each scheduler has two entry symbols: the plain kernel (its parameter list,
+// name and body are what they always were) and the _affine kernel, which
+// takes the epilogue as one more argument. The epilogue is not a parameter of
+// the plain kernels because even an empty struct takes a byte of the
+// kernel-argument block, and their body is shared as TEXT (the *_BODY macros,
+// with the epilogue expression as argument) rather than through one more
+// inlined function, which was tried and moved instructions in all 504 plain
+// kernels: they are to stay what they were, descriptor included.
+#define SPMM_GRID_BODY(EPILOGUE)                                              \
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;                     \
+  const int lane_in_group = threadIdx.x % GROUP;                              \
+  const int group_in_block = threadIdx.x / GROUP;                             \
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;                \
+  const bool active = !GUARD || (col0 < k);                                   \
+                                                                              \
+  /* XCD-aware workgroup remap (performance only): the dispatcher places     \
+     block b on XCD b%8, so remap block ids to give each XCD a CONTIGUOUS    \
+     range of work items: consecutive rows of a banded block then share the  \
+     XCD's private L2 window instead of interleaving across all 8 L2s.       \
+     Bijective form (cdna_hip_programming.md, XCD swizzle). */               \
+  int wg = blockIdx.x;                                                        \
+  if (xcd_remap) {                                                            \
+    const int nwg = gridDim.x;                                                \
+    const int q = nwg / 8, rm = nwg % 8;                                      \
+    const int xcd = blockIdx.x % 8, pos = blockIdx.x / 8;                     \
+    wg = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + pos;    \
+  }                                                                           \
+                                                                              \
+  spmm_process_items<T, VEC, GROUP, BETA, GUARD>(                             \
+      (int64_t)wg * GROUPS_PER_BLOCK + group_in_block, n_items,               \
+      (int64_t)gridDim.x * GROUPS_PER_BLOCK, item_row, item_begin, item_end,  \
+      X0, X1, C, k, col0, active, lane_in_group, nt_mode, EPILOGUE, a...)
 
 template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel(
@@ -533,29 +633,18 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel(
     const T *__restrict__ X0, const T *__restrict__ X1,
     T *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
     int nt_mode) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_block = threadIdx.x / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
+  SPMM_GRID_BODY(NoEpilogue{});
+}
 
-  // XCD-aware workgroup remap (performance only): the dispatcher places
-  // block b on XCD b%8, so remap block ids to give each XCD a CONTIGUOUS
-  // range of work items — consecutive rows of a banded block then share the
-  // XCD's private L2 window instead of interleaving across all 8 L2s.
-  // Bijective form (cdna_hip_programming.md §XCD swizzle).
-  int wg = blockIdx.x;
-  if (xcd_remap) {
-    const int nwg = gridDim.x;
-    const int q = nwg / 8, rm = nwg % 8;
-    const int xcd = blockIdx.x % 8, pos = blockIdx.x / 8;
-    wg = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + pos;
-  }
-
-  spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
-      (int64_t)wg * GROUPS_PER_BLOCK + group_in_block, n_items,
-      (int64_t)gridDim.x * GROUPS_PER_BLOCK, item_row, item_begin, item_end,
-      X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_affine(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end, int64_t n_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
+    int nt_mode, AffineEpilogue<T> ep) {
+  SPMM_GRID_BODY(ep);
 }
 
 // Per-XCD queue scheduler. The static grid-stride schedule above interleaves
@@ -575,6 +664,35 @@ __device__ __forceinline__ unsigned arrow_xcc_id() {
   return __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
 }
 
+#define SPMM_Q_BODY(EPILOGUE)                                                 \
+  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;                     \
+  const int lane_in_group = threadIdx.x % GROUP;                              \
+  const int group_in_block = threadIdx.x / GROUP;                             \
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;                \
+  const bool active = !GUARD || (col0 < k);                                   \
+  __shared__ int64_t s_base;                                                  \
+                                                                              \
+  const unsigned q0 = arrow_xcc_id() & 7;                                     \
+  for (unsigned qi = 0; qi < 8; ++qi) {                                       \
+    const unsigned q = (q0 + qi) & 7;                                         \
+    const int64_t lo = qseg[q], hi = qseg[q + 1];                             \
+    if (lo >= hi) continue;                                                   \
+    for (;;) {                                                                \
+      __syncthreads();                                                        \
+      if (threadIdx.x == 0) {                                                 \
+        s_base = lo + (int64_t)atomicAdd(&qctr[q * 32], chunk_items);         \
+      }                                                                       \
+      __syncthreads();                                                        \
+      const int64_t base = s_base;                                            \
+      if (base >= hi) break;                                                  \
+      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;  \
+      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(                         \
+          base + group_in_block, end, GROUPS_PER_BLOCK, item_row, item_begin, \
+          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode,       \
+          EPILOGUE, a...);                                                    \
+    }                                                                         \
+  }
+
 template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
     const A *__restrict__... a,
@@ -585,32 +703,20 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
     int chunk_items,
     const T *__restrict__ X0, const T *__restrict__ X1,
     T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
-  constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_block = threadIdx.x / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
-  __shared__ int64_t s_base;
+  SPMM_Q_BODY(NoEpilogue{})
+}
 
-  const unsigned q0 = arrow_xcc_id() & 7;
-  for (unsigned qi = 0; qi < 8; ++qi) {
-    const unsigned q = (q0 + qi) & 7;
-    const int64_t lo = qseg[q], hi = qseg[q + 1];
-    if (lo >= hi) continue;
-    for (;;) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        s_base = lo + (int64_t)atomicAdd(&qctr[q * 32], chunk_items);
-      }
-      __syncthreads();
-      const int64_t base = s_base;
-      if (base >= hi) break;
-      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
-          base + group_in_block, end, GROUPS_PER_BLOCK, item_row, item_begin,
-          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
-    }
-  }
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q_affine(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg, int32_t *__restrict__ qctr,
+    int chunk_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode,
+    AffineEpilogue<T> ep) {
+  SPMM_Q_BODY(ep)
 }
 
 // Per-WAVE queue grab variant of spmm_kernel_q: each 64-lane wave pulls its
@@ -620,6 +726,33 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q(
 // the slowest group of all 4 waves), at the cost of 4x the atomic rate
 // (fine: per-XCD counters, dequeue ~0.25-1.1 us uncontended and these are
 // thousands of grabs per segment, MI355X_MICROARCH.md §dequeue).
+#define SPMM_QW_BODY(EPILOGUE)                                                \
+  constexpr int GROUPS_PER_WAVE = 64 / GROUP;                                 \
+  const int lane = threadIdx.x & 63;                                          \
+  const int lane_in_group = threadIdx.x % GROUP;                              \
+  const int group_in_wave = lane / GROUP;                                     \
+  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;                \
+  const bool active = !GUARD || (col0 < k);                                   \
+                                                                              \
+  const unsigned q0 = arrow_xcc_id() & 7;                                     \
+  for (unsigned qi = 0; qi < 8; ++qi) {                                       \
+    const unsigned q = (q0 + qi) & 7;                                         \
+    const int64_t lo = qseg[q], hi = qseg[q + 1];                             \
+    if (lo >= hi) continue;                                                   \
+    for (;;) {                                                                \
+      int grab = 0;                                                           \
+      if (lane == 0) grab = atomicAdd(&qctr[q * 32], chunk_items);            \
+      grab = __shfl(grab, 0, 64);                                             \
+      const int64_t base = lo + grab;                                         \
+      if (base >= hi) break;                                                  \
+      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;  \
+      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(                         \
+          base + group_in_wave, end, GROUPS_PER_WAVE, item_row, item_begin,   \
+          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode,       \
+          EPILOGUE, a...);                                                    \
+    }                                                                         \
+  }
+
 template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
 __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw(
     const A *__restrict__... a,
@@ -630,30 +763,20 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw(
     int chunk_items,                  // per-WAVE grab size (items)
     const T *__restrict__ X0, const T *__restrict__ X1,
     T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode) {
-  constexpr int GROUPS_PER_WAVE = 64 / GROUP;
-  const int lane = threadIdx.x & 63;
-  const int lane_in_group = threadIdx.x % GROUP;
-  const int group_in_wave = lane / GROUP;
-  const int64_t col0 = col_off + (int64_t)lane_in_group * VEC;
-  const bool active = !GUARD || (col0 < k);
+  SPMM_QW_BODY(NoEpilogue{})
+}
 
-  const unsigned q0 = arrow_xcc_id() & 7;
-  for (unsigned qi = 0; qi < 8; ++qi) {
-    const unsigned q = (q0 + qi) & 7;
-    const int64_t lo = qseg[q], hi = qseg[q + 1];
-    if (lo >= hi) continue;
-    for (;;) {
-      int grab = 0;
-      if (lane == 0) grab = atomicAdd(&qctr[q * 32], chunk_items);
-      grab = __shfl(grab, 0, 64);
-      const int64_t base = lo + grab;
-      if (base >= hi) break;
-      const int64_t end = base + chunk_items < hi ? base + chunk_items : hi;
-      spmm_process_items<T, VEC, GROUP, BETA, GUARD>(
-          base + group_in_wave, end, GROUPS_PER_WAVE, item_row, item_begin,
-          item_end, X0, X1, C, k, col0, active, lane_in_group, nt_mode, a...);
-    }
-  }
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw_affine(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg, int32_t *__restrict__ qctr,
+    int chunk_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode,
+    AffineEpilogue<T> ep) {
+  SPMM_QW_BODY(ep)
 }
 
 template <typename T>
@@ -693,6 +816,133 @@ __global__ void spmm_finalise_bf16(uint16_t *__restrict__ C,
     *cp = bf16x8_pack(s);
     sp[0] = sp[1] = float4{0.f, 0.f, 0.f, 0.f};
   }
+}
+
+// Affine step, fp32 / f64 split rows, before the SpMM launches of one call:
+// the initialise pass that stands where zero_rows_kernel stands for the plain
+// entry points. C[row] = gamma * R[row] at beta = 0 (zero when R is null),
+// C[row] += gamma * R[row] at beta = 1; the items then add alpha * partial.
+template <typename T>
+__global__ void init_rows_affine_kernel(T *__restrict__ C,
+                                        const T *__restrict__ R, T gamma,
+                                        int beta,
+                                        const int32_t *__restrict__ rows,
+                                        int64_t n_rows, int64_t k) {
+  const int64_t total = n_rows * k;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k, j = t % k;
+    const int64_t at = (int64_t)rows[i] * k + j;
+    const T v = R ? gamma * R[at] : T(0);
+    C[at] = beta ? C[at] + v : v;
+  }
+}
+
+// Affine step, bf16 split rows: spmm_finalise_bf16 with the epilogue,
+// C[row] = bf16(alpha * sum + gamma * float(R[row]) + (BETA ? float(C[row])
+// : 0)), one rounding per element; the scratch is left zero.
+template <int BETA>
+__global__ void spmm_finalise_affine_bf16(uint16_t *__restrict__ C,
+                                          float *__restrict__ scratch,
+                                          const int32_t *__restrict__ rows,
+                                          int64_t n_rows, int64_t k8,
+                                          const uint16_t *__restrict__ R,
+                                          float alpha, float gamma) {
+  const int64_t total = n_rows * k8;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k8, j = t % k8;
+    float4 *sp = reinterpret_cast<float4 *>(scratch) + 2 * t;
+    const float4 s0 = sp[0], s1 = sp[1];
+    float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const int64_t at = (int64_t)rows[i] * k8 + j;
+    uint4 *cp = reinterpret_cast<uint4 *>(C) + at;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] *= alpha;
+    if (R) {
+      const Float8 r = bf16x8_unpack(reinterpret_cast<const uint4 *>(R)[at]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = fmaf(gamma, r[e], s[e]);
+    }
+    if constexpr (BETA == 1) {
+      const Float8 old = bf16x8_unpack(*cp);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] += old[e];
+    }
+    *cp = bf16x8_pack(s);
+    sp[0] = sp[1] = float4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// The stand-alone tail of the affine step, C = alpha * C + gamma * R over a
+// contiguous n x k block, for the engine layouts that do not fuse it into a
+// launch. A thread moves N elements (16 bytes when k allows, else one); bf16
+// computes in fp32 and rounds once. R is null when gamma == 0.
+template <typename T, int N>
+__global__ void axpby_rows_kernel(T *__restrict__ C, const T *__restrict__ R,
+                                  int64_t total_vec,
+                                  typename Prec<T>::Acc alpha,
+                                  typename Prec<T>::Acc gamma) {
+  using P = Prec<T>;
+  using Acc = typename P::Acc;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (N == 1) {
+      Acc o = alpha * C[t];
+      if (R) o = P::mad(gamma, R[t], o);
+      C[t] = o;
+    } else {
+      using XV = typename P::template XV<N>;
+      XV *cp = reinterpret_cast<XV *>(C) + t;
+      const auto &c = P::template unpack<N>(*cp);
+      Acc o[N];
+#pragma unroll
+      for (int j = 0; j < N; ++j) o[j] = alpha * c[j];
+      if (R) {
+        const XV rv = reinterpret_cast<const XV *>(R)[t];
+        const auto &r = P::template unpack<N>(rv);
+#pragma unroll
+        for (int j = 0; j < N; ++j) o[j] = P::mad(gamma, r[j], o[j]);
+      }
+      *cp = P::template pack<N>(o);
+    }
+  }
+}
+
+template <typename T>
+int launch_axpby(const char *who, T *C, const T *R, int64_t n, int64_t k,
+                 double alpha, double gamma, hipStream_t stream) {
+  using Acc = typename Prec<T>::Acc;
+  if (n < 0 || k <= 0 || (n > 0 && !C)) {
+    set_error(std::string(who) + ": bad arguments");
+    return -1;
+  }
+  if (n == 0) return 0;
+  if (!R && gamma != 0.0) {
+    set_error(std::string(who) + ": R is NULL but gamma is not 0");
+    return -4;
+  }
+  if (R && R == C) {
+    set_error(std::string(who) + ": R must not be C");
+    return -5;
+  }
+  constexpr int N = 16 / sizeof(T);
+  const bool vec = (k % N == 0);
+  const int64_t total = vec ? n * (k / N) : n * k;
+  const int threads = 256;
+  int blocks = (int)std::min<int64_t>((total + threads - 1) / threads, 16384);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(threads), 0, stream, C, R,
+                       total, (Acc)alpha, (Acc)gamma);
+  };
+  if constexpr (sizeof(T) == 2) {  // bf16: the caller checked k % 8 == 0
+    launch(axpby_rows_kernel<T, N>);
+  } else {
+    if (vec) launch(axpby_rows_kernel<T, N>);
+    else     launch(axpby_rows_kernel<T, 1>);
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -966,10 +1216,39 @@ SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
 }
 
 // a...: the structure's A-stream device pointers (Prec<T>::with_stream)
-template <typename T, int VEC, int GROUP, typename... A>
+// The entry symbol of a scheduler for the epilogue EP: the plain kernel or
+// its _affine form.
+template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
+          typename... A>
+constexpr auto grid_kernel() {
+  if constexpr (std::is_same_v<EP, NoEpilogue>)
+    return &spmm_kernel<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+}
+template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
+          typename... A>
+constexpr auto q_kernel() {
+  if constexpr (std::is_same_v<EP, NoEpilogue>)
+    return &spmm_kernel_q<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_q_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+}
+template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
+          typename... A>
+constexpr auto qw_kernel() {
+  if constexpr (std::is_same_v<EP, NoEpilogue>)
+    return &spmm_kernel_qw<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_qw_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+}
+
+// ep: NoEpilogue{} for the plain entry points, else the affine step's
+template <typename T, int VEC, int GROUP, typename EP, typename... A>
 int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
                    const T *X1, T *C, int64_t k, int beta, hipStream_t stream,
-                   const A *... a) {
+                   const EP &ep, const A *... a) {
+  constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
   constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
   const int nt_mode = plan.nt_mode;
   const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
@@ -986,58 +1265,72 @@ int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
   for (int64_t col_off = 0; col_off < k; col_off += span) {
     const bool guard = (col_off + span > k);
     auto run = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         a..., blk.item_row, blk.item_begin,
-                         blk.item_end, blk.n_items, X0, X1, C, k, col_off,
-                         blk.xcd_remap, nt_mode);
+      if constexpr (AFFINE) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                           a..., blk.item_row, blk.item_begin,
+                           blk.item_end, blk.n_items, X0, X1, C, k, col_off,
+                           blk.xcd_remap, nt_mode, ep);
+      } else {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                           a..., blk.item_row, blk.item_begin,
+                           blk.item_end, blk.n_items, X0, X1, C, k, col_off,
+                           blk.xcd_remap, nt_mode);
+      }
     };
     auto runq = [&](auto kern, int chunk) {
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
-                         a..., blk.item_row, blk.item_begin,
-                         blk.item_end, blk.qseg, blk.qctr, chunk,
-                         X0, X1, C, k, col_off, nt_mode);
+      if constexpr (AFFINE) {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                           a..., blk.item_row, blk.item_begin,
+                           blk.item_end, blk.qseg, blk.qctr, chunk,
+                           X0, X1, C, k, col_off, nt_mode, ep);
+      } else {
+        hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream,
+                           a..., blk.item_row, blk.item_begin,
+                           blk.item_end, blk.qseg, blk.qctr, chunk,
+                           X0, X1, C, k, col_off, nt_mode);
+      }
     };
     if (useq) {
       HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
       if (qwave) {
         if (beta == 0) {
-          if (guard) runq(spmm_kernel_qw<T, VEC, GROUP, 0, true, A...>, plan.chunk_items);
-          else       runq(spmm_kernel_qw<T, VEC, GROUP, 0, false, A...>, plan.chunk_items);
+          if (guard) runq(qw_kernel<EP, T, VEC, GROUP, 0, true, A...>(), plan.chunk_items);
+          else       runq(qw_kernel<EP, T, VEC, GROUP, 0, false, A...>(), plan.chunk_items);
         } else {
-          if (guard) runq(spmm_kernel_qw<T, VEC, GROUP, 1, true, A...>, plan.chunk_items);
-          else       runq(spmm_kernel_qw<T, VEC, GROUP, 1, false, A...>, plan.chunk_items);
+          if (guard) runq(qw_kernel<EP, T, VEC, GROUP, 1, true, A...>(), plan.chunk_items);
+          else       runq(qw_kernel<EP, T, VEC, GROUP, 1, false, A...>(), plan.chunk_items);
         }
       } else if (beta == 0) {
-        if (guard) runq(spmm_kernel_q<T, VEC, GROUP, 0, true, A...>, plan.chunk_items);
-        else       runq(spmm_kernel_q<T, VEC, GROUP, 0, false, A...>, plan.chunk_items);
+        if (guard) runq(q_kernel<EP, T, VEC, GROUP, 0, true, A...>(), plan.chunk_items);
+        else       runq(q_kernel<EP, T, VEC, GROUP, 0, false, A...>(), plan.chunk_items);
       } else {
-        if (guard) runq(spmm_kernel_q<T, VEC, GROUP, 1, true, A...>, plan.chunk_items);
-        else       runq(spmm_kernel_q<T, VEC, GROUP, 1, false, A...>, plan.chunk_items);
+        if (guard) runq(q_kernel<EP, T, VEC, GROUP, 1, true, A...>(), plan.chunk_items);
+        else       runq(q_kernel<EP, T, VEC, GROUP, 1, false, A...>(), plan.chunk_items);
       }
     } else if (beta == 0) {
-      if (guard) run(spmm_kernel<T, VEC, GROUP, 0, true, A...>);
-      else       run(spmm_kernel<T, VEC, GROUP, 0, false, A...>);
+      if (guard) run(grid_kernel<EP, T, VEC, GROUP, 0, true, A...>());
+      else       run(grid_kernel<EP, T, VEC, GROUP, 0, false, A...>());
     } else {
-      if (guard) run(spmm_kernel<T, VEC, GROUP, 1, true, A...>);
-      else       run(spmm_kernel<T, VEC, GROUP, 1, false, A...>);
+      if (guard) run(grid_kernel<EP, T, VEC, GROUP, 1, true, A...>());
+      else       run(grid_kernel<EP, T, VEC, GROUP, 1, false, A...>());
     }
     HIP_CHECK(hipGetLastError());
   }
   return 0;
 }
 
-template <typename T, int VEC, typename... A>
+template <typename T, int VEC, typename EP, typename... A>
 int launch_spmm_v(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
                   const T *X1, T *C, int64_t k, int beta, hipStream_t stream,
-                  const A *... a) {
+                  const EP &ep, const A *... a) {
   switch (plan.group) {
-    case 1:  return launch_spmm_vg<T, VEC, 1>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    case 2:  return launch_spmm_vg<T, VEC, 2>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    case 4:  return launch_spmm_vg<T, VEC, 4>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    case 8:  return launch_spmm_vg<T, VEC, 8>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    case 16: return launch_spmm_vg<T, VEC, 16>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    case 32: return launch_spmm_vg<T, VEC, 32>(blk, plan, X0, X1, C, k, beta, stream, a...);
-    default: return launch_spmm_vg<T, VEC, 64>(blk, plan, X0, X1, C, k, beta, stream, a...);
+    case 1:  return launch_spmm_vg<T, VEC, 1>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    case 2:  return launch_spmm_vg<T, VEC, 2>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    case 4:  return launch_spmm_vg<T, VEC, 4>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    case 8:  return launch_spmm_vg<T, VEC, 8>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    case 16: return launch_spmm_vg<T, VEC, 16>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    case 32: return launch_spmm_vg<T, VEC, 32>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
+    default: return launch_spmm_vg<T, VEC, 64>(blk, plan, X0, X1, C, k, beta, stream, ep, a...);
   }
 }
 
@@ -1074,14 +1367,20 @@ int ensure_bf16_scratch(CsrBlock &blk, int64_t k, hipStream_t stream) {
   return 0;
 }
 
-template <typename T>
+// ep: NoEpilogue{} (arrow_spmm*), or the affine step's R, alpha and gamma
+// (arrow_spmm*_affine*; `gamma_given` is the caller's gamma before the cast
+// to the accumulator type, for the R == NULL rule).
+template <typename T, typename EP = NoEpilogue>
 int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
-                   int64_t k, int beta, void *stream_v) {
+                   int64_t k, int beta, void *stream_v, const EP &ep = EP{},
+                   double gamma_given = 0.0) {
   using P = Prec<T>;
   using Other = Prec<std::conditional_t<P::dtype == 32, double, float>>;
   constexpr bool BF16 = std::is_same_v<T, uint16_t>;
+  constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
   constexpr int plan_dtype = BF16 ? 16 : P::dtype;
-  const std::string who = std::string("arrow_spmm") + P::suffix;
+  const std::string who =
+      std::string(AFFINE ? "arrow_spmm_affine" : "arrow_spmm") + P::suffix;
   auto it = g_blocks.find(handle);
   if (it == g_blocks.end()) {
     set_error(who + ": bad handle");
@@ -1105,12 +1404,38 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
   hipStream_t stream = (hipStream_t)stream_v;
   if constexpr (BF16) {
     if (!bf16_k_ok(who, k)) return -3;
+  }
+  if constexpr (AFFINE) {
+    if (!ep.R && gamma_given != 0.0) {
+      set_error(who + ": R is NULL but gamma is not 0");
+      return -4;
+    }
+    if (ep.R && ep.R == C_dev) {
+      set_error(who + ": R must not be C (X may alias R)");
+      return -5;
+    }
+    if (beta != 0 && beta != 1) {
+      set_error(who + ": beta must be 0 or 1, got " + std::to_string(beta));
+      return -6;
+    }
+  }
+  if constexpr (BF16) {
     if (ensure_bf16_scratch(blk, k, stream)) return -1;
   }
 
   // beta=0: split rows are accumulated with atomics, so pre-zero them (bf16
   // split rows go through the scratch and are written whole at the end).
-  if constexpr (!BF16) {
+  // Affine: the same pass initialises them with gamma * R (+ C) instead.
+  if constexpr (AFFINE && !BF16) {
+    if (blk.n_split_rows > 0 && (beta == 0 || ep.R)) {
+      const int64_t total = blk.n_split_rows * k;
+      int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+      hipLaunchKernelGGL(init_rows_affine_kernel<T>, dim3(blocks), dim3(256),
+                         0, stream, C_dev, ep.R, ep.gamma, beta,
+                         blk.split_rows, blk.n_split_rows, k);
+      HIP_CHECK(hipGetLastError());
+    }
+  } else if constexpr (!BF16) {
     if (beta == 0 && blk.n_split_rows > 0) {
       const int64_t total = blk.n_split_rows * k;
       int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
@@ -1124,15 +1449,15 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
       spmm_plan(k, blk.nnz, blk.queue_mode, blk.q_blocks, plan_dtype);
   const int rc = P::with_stream(blk, [&](const auto *... a) {
     if constexpr (BF16) {
-      return launch_spmm_v<T, 8>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+      return launch_spmm_v<T, 8>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, ep, a...);
     } else {
       if constexpr (P::dtype == 32) {
         if (plan.vec == 4)
-          return launch_spmm_v<T, 4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+          return launch_spmm_v<T, 4>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, ep, a...);
       }
       if (plan.vec == 2)
-        return launch_spmm_v<T, 2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
-      return launch_spmm_v<T, 1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, a...);
+        return launch_spmm_v<T, 2>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, ep, a...);
+      return launch_spmm_v<T, 1>(blk, plan, X0_dev, X1_dev, C_dev, k, beta, stream, ep, a...);
     }
   });
   if constexpr (BF16) {
@@ -1144,8 +1469,21 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
                            blk.bf16_scratch, blk.split_rows, blk.n_split_rows,
                            k / 8);
       };
-      if (beta == 0) fin(spmm_finalise_bf16<0>);
-      else           fin(spmm_finalise_bf16<1>);
+      auto fin_affine = [&](auto kern) {
+        if constexpr (AFFINE) {
+          hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, C_dev,
+                             blk.bf16_scratch, blk.split_rows,
+                             blk.n_split_rows, k / 8, ep.R, ep.alpha,
+                             ep.gamma);
+        }
+      };
+      if constexpr (AFFINE) {
+        if (beta == 0) fin_affine(spmm_finalise_affine_bf16<0>);
+        else           fin_affine(spmm_finalise_affine_bf16<1>);
+      } else {
+        if (beta == 0) fin(spmm_finalise_bf16<0>);
+        else           fin(spmm_finalise_bf16<1>);
+      }
       HIP_CHECK(hipGetLastError());
     }
   }
@@ -1165,6 +1503,17 @@ int spmm_plan_export(const char *who, int dtype, int64_t k, int64_t nnz,
       p.n_launches};
   for (int i = 0; i < n_out && i < ARROW_PLAN_FIELDS; ++i) out[i] = fields[i];
   return ARROW_PLAN_FIELDS;
+}
+
+// arrow_spmm*_affine*: the caller's double alpha and gamma, cast once to the
+// accumulator type of T
+template <typename T>
+int spmm_affine(int64_t handle, const T *X0, const T *X1, T *C, const T *R,
+                int64_t k, double alpha, double gamma, int beta,
+                void *stream) {
+  using Acc = typename Prec<T>::Acc;
+  const AffineEpilogue<T> ep{R, (Acc)alpha, (Acc)gamma};
+  return spmm_dual_impl<T>(handle, X0, X1, C, k, beta, stream, ep, gamma);
 }
 
 }  // namespace
@@ -1523,6 +1872,77 @@ int arrow_spmm_plan_bf16(int64_t k, int64_t nnz, int queue_mode, int32_t *out,
                          int n_out) {
   return spmm_plan_export("arrow_spmm_plan_bf16", 16, k, nnz, queue_mode, out,
                           n_out);
+}
+
+// Affine step (ABI 1005): C = alpha * (A @ X) + gamma * R + beta * C, fused
+// into the write-back of the same launches the plain entry points make.
+int arrow_spmm_dual_affine(int64_t handle, const float *X0_dev,
+                           const float *X1_dev, float *C_dev,
+                           const float *R_dev, int64_t k, double alpha,
+                           double gamma, int beta, void *stream) {
+  return spmm_affine<float>(handle, X0_dev, X1_dev, C_dev, R_dev, k, alpha,
+                            gamma, beta, stream);
+}
+
+int arrow_spmm_affine(int64_t handle, const float *X_dev, float *C_dev,
+                      const float *R_dev, int64_t k, double alpha,
+                      double gamma, int beta, void *stream) {
+  return spmm_affine<float>(handle, X_dev, X_dev, C_dev, R_dev, k, alpha,
+                            gamma, beta, stream);
+}
+
+int arrow_spmm_dual_affine_f64(int64_t handle, const double *X0_dev,
+                               const double *X1_dev, double *C_dev,
+                               const double *R_dev, int64_t k, double alpha,
+                               double gamma, int beta, void *stream) {
+  return spmm_affine<double>(handle, X0_dev, X1_dev, C_dev, R_dev, k, alpha,
+                             gamma, beta, stream);
+}
+
+int arrow_spmm_affine_f64(int64_t handle, const double *X_dev, double *C_dev,
+                          const double *R_dev, int64_t k, double alpha,
+                          double gamma, int beta, void *stream) {
+  return spmm_affine<double>(handle, X_dev, X_dev, C_dev, R_dev, k, alpha,
+                             gamma, beta, stream);
+}
+
+int arrow_spmm_dual_affine_bf16(int64_t handle, const uint16_t *X0_dev,
+                                const uint16_t *X1_dev, uint16_t *C_dev,
+                                const uint16_t *R_dev, int64_t k,
+                                double alpha, double gamma, int beta,
+                                void *stream) {
+  return spmm_affine<uint16_t>(handle, X0_dev, X1_dev, C_dev, R_dev, k, alpha,
+                               gamma, beta, stream);
+}
+
+int arrow_spmm_affine_bf16(int64_t handle, const uint16_t *X_dev,
+                           uint16_t *C_dev, const uint16_t *R_dev, int64_t k,
+                           double alpha, double gamma, int beta,
+                           void *stream) {
+  return spmm_affine<uint16_t>(handle, X_dev, X_dev, C_dev, R_dev, k, alpha,
+                               gamma, beta, stream);
+}
+
+int arrow_axpby_rows_f32(float *C_dev, const float *R_dev, int64_t n,
+                         int64_t k, double alpha, double gamma,
+                         void *stream) {
+  return launch_axpby<float>("arrow_axpby_rows_f32", C_dev, R_dev, n, k,
+                             alpha, gamma, (hipStream_t)stream);
+}
+
+int arrow_axpby_rows_f64(double *C_dev, const double *R_dev, int64_t n,
+                         int64_t k, double alpha, double gamma,
+                         void *stream) {
+  return launch_axpby<double>("arrow_axpby_rows_f64", C_dev, R_dev, n, k,
+                              alpha, gamma, (hipStream_t)stream);
+}
+
+int arrow_axpby_rows_bf16(uint16_t *C_dev, const uint16_t *R_dev, int64_t n,
+                          int64_t k, double alpha, double gamma,
+                          void *stream) {
+  if (!bf16_k_ok("arrow_axpby_rows_bf16", k)) return -3;
+  return launch_axpby<uint16_t>("arrow_axpby_rows_bf16", C_dev, R_dev, n, k,
+                                alpha, gamma, (hipStream_t)stream);
 }
 
 // bf16 routing: the pure copies move each row as k/2 floats through the fp32

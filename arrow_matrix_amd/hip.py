@@ -117,6 +117,26 @@ def _load():
         fn = getattr(lib, name + '_bf16')
         fn.argtypes = getattr(lib, name + '_f32').argtypes
         fn.restype = ctypes.c_int
+    # affine step (ABI 1005): (handle, X0[, X1], C, R, k, alpha, gamma, beta,
+    # stream) and the stand-alone tail (C, R, n, k, alpha, gamma, stream)
+    for sfx in ('', '_f64', '_bf16'):
+        fn = getattr(lib, 'arrow_spmm_affine' + sfx)
+        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
+                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        fn = getattr(lib, 'arrow_spmm_dual_affine' + sfx)
+        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                       ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+    for sfx in ('_f32', '_f64', '_bf16'):
+        fn = getattr(lib, 'arrow_axpby_rows' + sfx)
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                       ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                       ctypes.c_void_p]
+        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -217,9 +237,23 @@ class CsrBlockGPU:
             _suffix(self.dtype if feat_dtype is None else feat_dtype)]
         return getattr(_load(), name + sfx), name + sfx
 
+    @staticmethod
+    def _is_affine(alpha, gamma, R_ptr) -> bool:
+        return alpha != 1.0 or gamma != 0.0 or bool(R_ptr)
+
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0,
-             feat_dtype=None):
-        """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr())."""
+             feat_dtype=None, alpha: float = 1.0, gamma: float = 0.0,
+             R_ptr: int = 0):
+        """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr()).
+        With alpha, gamma or R_ptr given: the fused affine step
+        C = alpha * (A @ X) + gamma * R + beta * C (arrow_spmm_affine*;
+        R_ptr 0 needs gamma 0). Without them the plain entry point is
+        called, as before."""
+        if self._is_affine(alpha, gamma, R_ptr):
+            fn, name = self._entry('arrow_spmm_affine', feat_dtype)
+            _check(fn(self._handle, X_ptr, C_ptr, R_ptr or None, k,
+                      float(alpha), float(gamma), beta, stream), name)
+            return
         fn, name = self._entry('arrow_spmm', feat_dtype)
         _check(fn(self._handle, X_ptr, C_ptr, k, beta, stream), name)
 
@@ -238,9 +272,16 @@ class CsrBlockGPU:
                "arrow_csr_set_qblocks")
 
     def spmm_dual(self, X0_ptr: int, X1_ptr: int, C_ptr: int, k: int,
-                  beta: int, stream: int = 0, feat_dtype=None):
+                  beta: int, stream: int = 0, feat_dtype=None,
+                  alpha: float = 1.0, gamma: float = 0.0, R_ptr: int = 0):
         """Fused dual-operand SpMM: negative column indices (encoded at
-        upload as -(idx+1)) read X1 (see include/arrow_spmm.h)."""
+        upload as -(idx+1)) read X1 (see include/arrow_spmm.h). alpha, gamma
+        and R_ptr as in spmm (arrow_spmm_dual_affine*)."""
+        if self._is_affine(alpha, gamma, R_ptr):
+            fn, name = self._entry('arrow_spmm_dual_affine', feat_dtype)
+            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, R_ptr or None, k,
+                      float(alpha), float(gamma), beta, stream), name)
+            return
         fn, name = self._entry('arrow_spmm_dual', feat_dtype)
         _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, k, beta, stream), name)
 
@@ -293,6 +334,15 @@ def permute_add_rows(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k,
                      stream=0, dtype=np.float32):
     fn, name = _route('permute_add_rows', dtype)
     _check(fn(dst_ptr, src_ptr, dst_idx_ptr, src_idx_ptr, n, k, stream), name)
+
+
+def axpby_rows(C_ptr: int, R_ptr: int, n: int, k: int, alpha: float,
+               gamma: float, stream: int = 0, dtype=np.float32):
+    """C = alpha * C + gamma * R over n contiguous rows of width k (the
+    stand-alone tail of the affine step; R_ptr 0 needs gamma 0)."""
+    fn, name = _route('axpby_rows', dtype)
+    _check(fn(C_ptr, R_ptr or None, n, k, float(alpha), float(gamma), stream),
+           name)
 
 
 PLAN_FIELDS = ('vec', 'group', 'scheduler', 'nt_mode', 'chunk_items',

@@ -294,6 +294,76 @@ int arrow_permute_add_rows_bf16(uint16_t *dst_dev, const uint16_t *src_dev,
                                 const int64_t *src_idx_dev, int64_t n,
                                 int64_t k, void *stream);
 
+/* ---------------------------------------------------------------------
+ * Affine step (ABI 1005). The workloads that iterate an SpMM (PageRank,
+ * APPNP / label propagation, damped diffusion, Chebyshev filters) want
+ *
+ *     C[row] = alpha * (A @ X)[row] + gamma * R[row] + beta * C[row]
+ *
+ * for every output row the structure writes, with beta 0 or 1. The
+ * reference has no such call (its callers run an elementwise pass after
+ * `A @ X`); here the step is fused into the write-back of the SAME launches
+ * the plain entry points make: one extra read of R, C still written once.
+ *
+ * R is a row-major matrix of the feature type, shaped like C and indexed by
+ * OUTPUT row (after row_ids). Empty rows yield gamma * R[row] (+ C[row]).
+ * alpha and gamma are doubles in every precision and are applied in the
+ * accumulator type: float for fp32 and bf16 features, double for float64.
+ * bf16: one rounding per element, split rows included (their finalise pass
+ * computes bf16(alpha * sum + gamma * float(R) + (beta ? float(C) : 0))).
+ * fp32 / f64 split rows: the pre-launch pass writes gamma * R (adds it at
+ * beta = 1) and the items add alpha * partial with the hardware atomic.
+ *
+ * Rules; a broken one returns a negative code, sets arrow_last_error(),
+ * launches nothing and leaves C untouched:
+ *   - R == NULL is allowed only when gamma == 0; R is then never read;
+ *   - R == C is refused (X may alias R);
+ *   - beta other than 0 or 1 is refused;
+ *   - a handle of the other precision, and bf16 k % 8 != 0, are refused
+ *     exactly as on the plain entry points.
+ *
+ * The launch plan is the plain one: arrow_spmm_plan / _f64 / _bf16 are
+ * unchanged and describe an affine launch too. (alpha, gamma, R) =
+ * (1, 0, NULL) computes what the plain entry point computes, bit for bit.
+ * The bf16 warm-up rule before stream capture applies unchanged.
+ * ------------------------------------------------------------------- */
+int arrow_spmm_affine(int64_t handle, const float *X_dev, float *C_dev,
+                      const float *R_dev, int64_t k, double alpha,
+                      double gamma, int beta, void *stream);
+int arrow_spmm_dual_affine(int64_t handle, const float *X0_dev,
+                           const float *X1_dev, float *C_dev,
+                           const float *R_dev, int64_t k, double alpha,
+                           double gamma, int beta, void *stream);
+int arrow_spmm_affine_f64(int64_t handle, const double *X_dev, double *C_dev,
+                          const double *R_dev, int64_t k, double alpha,
+                          double gamma, int beta, void *stream);
+int arrow_spmm_dual_affine_f64(int64_t handle, const double *X0_dev,
+                               const double *X1_dev, double *C_dev,
+                               const double *R_dev, int64_t k, double alpha,
+                               double gamma, int beta, void *stream);
+int arrow_spmm_affine_bf16(int64_t handle, const uint16_t *X_dev,
+                           uint16_t *C_dev, const uint16_t *R_dev, int64_t k,
+                           double alpha, double gamma, int beta,
+                           void *stream);
+int arrow_spmm_dual_affine_bf16(int64_t handle, const uint16_t *X0_dev,
+                                const uint16_t *X1_dev, uint16_t *C_dev,
+                                const uint16_t *R_dev, int64_t k,
+                                double alpha, double gamma, int beta,
+                                void *stream);
+
+/* The stand-alone tail of the affine step, for results that no single
+ * launch finishes: C = alpha * C + gamma * R over n contiguous rows of
+ * width k (device, row-major). bf16 (k % 8 == 0) moves 16-byte lanes,
+ * computes in fp32 and rounds once. R == NULL only with gamma == 0; R == C
+ * is refused; n == 0 is a no-op. */
+int arrow_axpby_rows_f32(float *C_dev, const float *R_dev, int64_t n,
+                         int64_t k, double alpha, double gamma, void *stream);
+int arrow_axpby_rows_f64(double *C_dev, const double *R_dev, int64_t n,
+                         int64_t k, double alpha, double gamma, void *stream);
+int arrow_axpby_rows_bf16(uint16_t *C_dev, const uint16_t *R_dev, int64_t n,
+                          int64_t k, double alpha, double gamma,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

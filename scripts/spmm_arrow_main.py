@@ -41,7 +41,17 @@ def main() -> None:
                         help='load the .npy (indptr/indices/data) format; '
                              'False loads the legacy .npz format')
 
+    # not a reference flag
+    parser.add_argument('--damping', type=float, default=None, metavar='D',
+                        help='iterate X <- D*A@X + (1-D)*X0 with the initial '
+                             'features X0 as residual (default: off, plain '
+                             'X <- A@X on fresh features)')
+
     args = vars(parser.parse_args())
+    # off: the printed arguments and the run are what they were without it
+    damping = args.pop('damping')
+    if damping is not None:
+        args['damping'] = damping
     comm = default_comm()
     utils.mpi_print(comm.rank, str(args))
 
@@ -61,7 +71,9 @@ def main() -> None:
                            args['ba_neighbors'],
                            args['wandb_key'],
                            slim=args['slim'],
-                           npy_format=args['npy'])
+                           npy_format=args['npy'],
+                           **({} if damping is None
+                              else {'damping': damping}))
 
 
 if __name__ == '__main__':
