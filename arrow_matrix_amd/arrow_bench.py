@@ -31,12 +31,19 @@ def bench_spmm(path: Union[str, None],
                datatype=np.float32,
                slim: bool = True,
                npy_format: bool = True,
-               damping: float = None):
+               damping: float = None,
+               tol: float = None):
     """damping=D (not in the reference; default off, nothing changes without
     it) iterates the damped step X <- D * A@X + (1 - D) * X0 instead of
     drawing fresh features every iteration: X0, the first iteration's
     features, is the residual of the engine's affine step (PageRank's
-    shape). Single process only."""
+    shape). Single process only. tol=T (needs damping) tracks the step norms
+    and stops after the first iteration with ||X_new - X_old|| / ||X_new||
+    <= T, printing the steps taken and the last ratio; without it nothing
+    changes."""
+    if tol is not None and damping is None:
+        raise ValueError("bench_spmm: tol needs damping (a plain run draws "
+                         "fresh features every iteration)")
     assert width > 0
     assert not slim or blocked  # reference arrow_dec_mpi.py:131
     comm = default_comm()
@@ -86,6 +93,9 @@ def bench_spmm(path: Union[str, None],
     wb_logging.log({"init_time": time.perf_counter() - tic})
 
     eng0 = arrow.engines[0]
+    if tol is not None:
+        arrow.track_step_norms()
+    steps_done, rel = 0, float('nan')
     for i in range(iterations):
         # fresh features on matrix 0 each iteration (arrow_bench.py:113-116)
         rows = max(eng0.n_owned, 1) * width
@@ -121,6 +131,15 @@ def bench_spmm(path: Union[str, None],
         if int(flag.item()):
             print("RANK", comm.rank, "FAILED", flush=True)
             break
+        if tol is not None:
+            d, c = arrow.last_step_norms()
+            steps_done = i + 1
+            rel = d / c if c > 0.0 else (0.0 if d == 0.0 else float('inf'))
+            if rel <= tol:
+                break
+    if tol is not None and comm.rank == 0:
+        print("STEPS", steps_done, "REL", repr(rel), "TOL", repr(tol),
+              flush=True)
 
     wb_logging.finish()
     comm.barrier()

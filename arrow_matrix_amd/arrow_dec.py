@@ -75,6 +75,11 @@ class ArrowDecompositionMPI:
         self._fold_maps: Optional[List] = None
         # affine step (set_affine_step): part 0's (alpha, gamma, R) or None
         self._affine = None
+        # step norms (track_step_norms): at L == 1 part 0's engine measures
+        # its own step; at L > 1 this accumulator takes one stand-alone pass
+        # over part 0's finished result
+        self._norms_on = False
+        self._norm_acc = None
         self._initialize_all_to_all_tables()
 
     @property
@@ -407,11 +412,82 @@ class ArrowDecompositionMPI:
         return (self._folded is not None
                 and self.engines[0].backend.device == 'cuda')
 
+    # -- step norms ----------------------------------------------------------
+
+    def track_step_norms(self, on: bool = True) -> None:
+        """Make every later step() also measure itself: sum (C - X)^2 and
+        sum C^2 over part 0's finished result C against part 0's features X
+        before the step (DESIGN.md §step norms). L = 1 measures inside part
+        0's own spmm() (fused into the default single launch on the GPU);
+        both folds and the sequential L > 1 layout run one stand-alone pass
+        after the last launch, aggregate or tail. The accumulator is
+        allocated here, never inside step(). Single process only."""
+        if on and self.comm.size > 1:
+            raise NotImplementedError(
+                "step norms are single-process only: block row 0 would have "
+                "to be counted exactly once across ranks, and there is no "
+                "multi-GPU rig to validate that")
+        eng0 = self.engines[0]
+        self._norms_on = bool(on)
+        if self.decomposition_length == 1:
+            eng0.track_step_norms(on)
+        else:
+            self._norm_acc = eng0.backend.norm_acc() if on else None
+
+    def last_step_norms(self):
+        """(||C - X_prev||_2, ||C||_2) of the last step() as floats.
+        Synchronises and reads 16 bytes."""
+        if not self._norms_on:
+            raise RuntimeError("last_step_norms: call track_step_norms() "
+                               "before the step")
+        if self.decomposition_length == 1:
+            return self.engines[0].last_step_norms()
+        d2, c2 = self._norm_acc.tolist()
+        return float(np.sqrt(d2)), float(np.sqrt(c2))
+
+    def iterate(self, max_steps: int, tol: float = None,
+                check_every: int = 1):
+        """Run step() up to max_steps times, feeding part 0's result back as
+        its features after every step, and return (steps_done, rel) with
+        rel = ||X_new - X_old||_2 / ||X_new||_2 of the last step read. rel is
+        read every check_every steps (and after the last one); the loop stops
+        when tol is not None and rel <= tol. Turns step-norm tracking on.
+        Single process only."""
+        if self.comm.size > 1:
+            raise NotImplementedError(
+                "iterate is single-process only, as the step norms it reads")
+        if max_steps < 1 or check_every < 1:
+            raise ValueError("iterate: max_steps and check_every must be >= 1")
+        if not self._norms_on:
+            self.track_step_norms()
+        eng0 = self.engines[0]
+        rel = float('nan')
+        for t in range(1, max_steps + 1):
+            self.step()
+            eng0.set_features(eng0.result_tile())
+            if t % check_every == 0 or t == max_steps:
+                d, c = self.last_step_norms()
+                rel = d / c if c > 0.0 else (0.0 if d == 0.0 else float('inf'))
+                if tol is not None and rel <= tol:
+                    return t, rel
+        return max_steps, rel
+
     # -- iteration -----------------------------------------------------------
 
     def step(self) -> None:
         """One iteration; with an affine step set, X <- alpha*A@X + gamma*R
-        (see _step_plain for the plain step)."""
+        (see _step_affine for the step itself). With step norms tracked at
+        L > 1, one pass over part 0's finished result follows."""
+        if self._norm_acc is None:
+            self._step_affine()
+            return
+        eng0 = self.engines[0]
+        X_pre = eng0.feature_tile()  # its buffer is not written by the step
+        self._step_affine()
+        self._norm_acc.zero_()
+        eng0.backend.diffnorm_rows(eng0.C_i, X_pre, self._norm_acc)
+
+    def _step_affine(self) -> None:
         if self._affine is None:
             self._step_plain()
             return

@@ -119,6 +119,9 @@ class ArrowSlimMPI(ArrowMatrix):
         # at gamma == 0); never swapped with X / C
         self._affine = None
         self._R: Optional[torch.Tensor] = None
+        # step norms (track_step_norms): None, or the backend's two-double
+        # accumulator {sum (C - X)^2, sum C^2} of the last spmm()
+        self._norm_acc: Optional[torch.Tensor] = None
 
     # -- data loading --------------------------------------------------------
 
@@ -603,6 +606,38 @@ class ArrowSlimMPI(ArrowMatrix):
         # a cached X_0 (the allreduce_x0 fast path) holds the plain C_0
         self._x0_valid = False
 
+    # -- step norms ----------------------------------------------------------
+
+    def track_step_norms(self, on: bool = True) -> None:
+        """Make every later spmm() also measure its step: sum (C - X)^2 and
+        sum C^2 over this rank's whole stripe, X being the features the step
+        read (DESIGN.md §step norms). The two-double accumulator is allocated
+        here, never inside spmm(), and spmm() reads nothing back: a tracked
+        step stays capture-legal. On the GPU the default single-launch layout
+        measures in its write-back (arrow_spmm_dual_affine_norm*); every other
+        layout runs one stand-alone pass over the finished result. Single
+        process only."""
+        if on and self.comm.size > 1:
+            raise NotImplementedError(
+                "step norms are single-process only: at world>1 block row 0 "
+                "would have to be counted exactly once across ranks, and "
+                "there is no multi-GPU rig to validate that")
+        self._norm_acc = self.backend.norm_acc() if on else None
+
+    def last_step_norms(self):
+        """(||C - X_prev||_2, ||C||_2) of the last spmm() as floats.
+        Synchronises and reads the 16 bytes of the accumulator."""
+        if self._norm_acc is None:
+            raise RuntimeError("last_step_norms: call track_step_norms() "
+                               "before the step")
+        d2, c2 = self._norm_acc.tolist()
+        return float(np.sqrt(d2)), float(np.sqrt(c2))
+
+    def _measure_result(self) -> None:
+        """The stand-alone pass: the layouts whose result no single launch
+        finishes (and the cpu device)."""
+        self.backend.diffnorm_rows(self.C_i, self.X_i, self._norm_acc)
+
     def _select_result_buffer(self):
         if self.X_i is None or self.C_i.data_ptr() != self.X_i.data_ptr():
             return
@@ -654,6 +689,8 @@ class ArrowSlimMPI(ArrowMatrix):
                 f"engine was built for device={self.device!r}; got {device!r}")
         self._select_result_buffer()
         w = self.width
+        if self._norm_acc is not None:
+            self._norm_acc.zero_()  # on the launch stream
 
         # X_0 broadcast (arrow_slim_mpi.py:265-273); owner of block 0 is
         # rank 0. Overlapped: the row-0 launch below reads only the stripe,
@@ -709,6 +746,9 @@ class ArrowSlimMPI(ArrowMatrix):
         if self._affine is not None and not (
                 self.backend.device == 'cuda' and self._A_all is not None):
             self._affine_tail()
+        if self._norm_acc is not None and not (
+                self.backend.device == 'cuda' and self._A_all is not None):
+            self._measure_result()
 
     def _timed(self, fn, nnz, c_rows, x_rows):
         """HIP-event instrumentation for the roofline (bench.py)."""
@@ -749,6 +789,16 @@ class ArrowSlimMPI(ArrowMatrix):
             # single process: whole matrix in ONE fused launch, C in place;
             # X_0 == X_i[:w] so the second operand is the stripe itself
             h = self._A_all
+            if self._norm_acc is not None:
+                # the launch writes every row of C_i and measures each against
+                # the features it read, with or without an affine step
+                alpha, gamma, R = self._affine or (1.0, 0.0, None)
+                norm = (self.X_i, self._norm_acc)
+                self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i,
+                                                 self.C_i, 0, alpha, gamma, R,
+                                                 norm=norm),
+                            h.nnz, self.n_owned * w, h.x_rows)
+                return
             if self._affine is not None:
                 # the affine step rides in this launch's write-back
                 alpha, gamma, R = self._affine

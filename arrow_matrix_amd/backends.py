@@ -87,6 +87,19 @@ class CpuBackend:
         if R is not None:
             c += dt(gamma) * R.numpy()
 
+    def diffnorm_rows(self, C: torch.Tensor, D, acc: torch.Tensor):
+        """acc[0] += sum (C - D)^2, acc[1] += sum C^2, the definition of the
+        step norms in float64 (D None means 0); the parity reference of the
+        GPU kernels."""
+        c = C.numpy().astype(np.float64)
+        d = D.numpy().astype(np.float64) if D is not None else 0.0
+        acc[0] += float(np.square(c - d).sum())
+        acc[1] += float(np.square(c).sum())
+
+    def norm_acc(self) -> torch.Tensor:
+        """The two-double accumulator of the step norms."""
+        return torch.zeros(2, dtype=torch.float64)
+
     def synchronize(self):
         pass
 
@@ -118,6 +131,10 @@ class GpuBackend:
         self.torch_device = torch.device('cuda', device_index)
         # Loading the library here makes a missing .so fail at construction.
         hip.set_device(device_index)
+        # how often the measuring entry points were called: fused launches
+        # and stand-alone passes (the engine tests read them)
+        self.norm_launches = 0
+        self.diffnorm_launches = 0
 
     def _stream(self) -> int:
         return torch.cuda.current_stream(self.device_index).cuda_stream
@@ -149,12 +166,32 @@ class GpuBackend:
         return dict(alpha=alpha, gamma=gamma,
                     R_ptr=R.data_ptr() if R is not None else 0)
 
+    @staticmethod
+    def _norm_kw(norm, C):
+        """norm=(D, acc) as the pointer pair hip.py takes (D None: D = 0)."""
+        if norm is None:
+            return {}
+        D, acc = norm
+        assert D is None or (D.is_contiguous() and D.shape == C.shape
+                             and D.dtype == C.dtype)
+        assert acc.dtype == torch.float64 and acc.numel() == 2 \
+            and acc.device == C.device
+        return dict(norm=(D.data_ptr() if D is not None else 0,
+                          acc.data_ptr()))
+
     def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int,
-                   alpha: float = 1.0, gamma: float = 0.0, R=None):
+                   alpha: float = 1.0, gamma: float = 0.0, R=None, norm=None):
+        """norm=(D, acc): the launch also adds sum (C - D)^2 and sum C^2 into
+        the two float64 of the device tensor acc (beta 0 only)."""
         assert X.is_contiguous() and C.is_contiguous()
+        kw = self._affine_kw(alpha, gamma, R, C)
+        if norm is not None:
+            self.norm_launches += 1
+            kw = dict(alpha=alpha, gamma=gamma,
+                      R_ptr=R.data_ptr() if R is not None else 0,
+                      **self._norm_kw(norm, C))
         block.spmm(X.data_ptr(), C.data_ptr(), C.shape[1], beta, self._stream(),
-                   feat_dtype=self.feat_dtype,
-                   **self._affine_kw(alpha, gamma, R, C))
+                   feat_dtype=self.feat_dtype, **kw)
 
     def upload_arrays(self, shape, indptr, indices, data, row_ids=None,
                       col_items=False) -> hip.CsrBlockGPU:
@@ -164,12 +201,31 @@ class GpuBackend:
 
     def spmm_dual(self, block: hip.CsrBlockGPU, X0: torch.Tensor,
                   X1: torch.Tensor, C: torch.Tensor, beta: int,
-                  alpha: float = 1.0, gamma: float = 0.0, R=None):
+                  alpha: float = 1.0, gamma: float = 0.0, R=None, norm=None):
         assert X0.is_contiguous() and X1.is_contiguous() and C.is_contiguous()
+        kw = self._affine_kw(alpha, gamma, R, C)
+        if norm is not None:
+            self.norm_launches += 1
+            kw = dict(alpha=alpha, gamma=gamma,
+                      R_ptr=R.data_ptr() if R is not None else 0,
+                      **self._norm_kw(norm, C))
         block.spmm_dual(X0.data_ptr(), X1.data_ptr(), C.data_ptr(),
                         C.shape[1], beta, self._stream(),
-                        feat_dtype=self.feat_dtype,
-                        **self._affine_kw(alpha, gamma, R, C))
+                        feat_dtype=self.feat_dtype, **kw)
+
+    def diffnorm_rows(self, C: torch.Tensor, D, acc: torch.Tensor):
+        """acc[0] += sum (C - D)^2, acc[1] += sum C^2 over the rows of C
+        (arrow_diffnorm_rows_*; D None means 0)."""
+        assert C.is_contiguous()
+        self.diffnorm_launches += 1
+        if C.shape[0]:
+            hip.diffnorm_rows(C.data_ptr(), self._norm_kw((D, acc), C)['norm'][0],
+                              C.shape[0], C.shape[1], acc.data_ptr(),
+                              self._stream(), dtype=self.feat_dtype)
+
+    def norm_acc(self) -> torch.Tensor:
+        """The two-double device accumulator of the step norms."""
+        return torch.zeros(2, dtype=torch.float64, device=self.torch_device)
 
     def axpby_rows(self, C: torch.Tensor, R, alpha: float, gamma: float):
         """C = alpha * C + gamma * R in place (arrow_axpby_rows_*)."""

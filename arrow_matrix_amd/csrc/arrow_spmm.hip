@@ -47,7 +47,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1005  // affine step (arrow_spmm*_affine*, arrow_axpby_rows_*)
+#define ARROW_ABI_VERSION 1006  // step norms (arrow_spmm*_affine_norm*, arrow_diffnorm_rows_*)
 
 namespace {
 
@@ -345,6 +345,68 @@ template <typename T> struct AffineEpilogue {
   const T *R;
   typename Prec<T>::Acc alpha, gamma;
 };
+// AffineNormEpilogue is the affine step that also measures it: every
+// non-split row adds sum (c - d)^2 and sum c^2 over its stored values c and
+// the stored values d of D[row] (indexed like R; null means d = 0). c - d is
+// formed in the accumulator type, squares and sums are double. Beta is 0. The
+// kernel argument is AffineNormEpilogue; the items see AffineNormLane, which
+// adds the thread's two running sums (they live across all of its items and
+// leave through norm_block_reduce at kernel exit).
+template <typename T> struct AffineNormEpilogue {
+  const T *R;
+  typename Prec<T>::Acc alpha, gamma;
+  const T *D;
+  double *acc;  // device, two doubles, added into
+};
+template <typename T> struct AffineNormLane : AffineNormEpilogue<T> {
+  double *sums;  // the thread's own {sum (c - d)^2, sum c^2}
+};
+
+// sums[0] += sum (c - d)^2, sums[1] += sum c^2 over N stored values
+template <typename Acc, int N, typename CV, typename DV>
+__device__ __forceinline__ void norm_add(double *sums, const CV &c,
+                                         const DV &d) {
+  // each square is rounded to double, then added: with d = 0 a thread's two
+  // sums take the same terms in the same order and stay equal bit for bit (a
+  // square fused into one sum's add and not the other's would part them).
+  // The workgroups' atomics land in an order of their own per accumulator,
+  // so the totals are equal only where the sums are exact.
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const Acc diff = Acc(c[j]) - Acc(d[j]);
+    sums[0] += (double)diff * (double)diff;
+    sums[1] += (double)c[j] * (double)c[j];
+  }
+}
+
+// The exit of every kernel that measures: all 256 threads of the workgroup
+// arrive here (no path returns early), the waves reduce by shuffle, the
+// workgroup through LDS, and thread 0 adds the two totals with the hardware
+// float64 atomic.
+__device__ __forceinline__ void norm_block_reduce(double s0, double s1,
+                                                  double *acc) {
+  __shared__ double part[2][BLOCK_THREADS / 64];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s0 += __shfl_down(s0, off, 64);
+    s1 += __shfl_down(s1, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    part[0][threadIdx.x >> 6] = s0;
+    part[1][threadIdx.x >> 6] = s1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < BLOCK_THREADS / 64; ++w) {
+      s0 += part[0][w];
+      s1 += part[1][w];
+    }
+    atomicAdd(acc, s0);
+    atomicAdd(acc + 1, s1);
+  }
+}
 
 template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename EP,
           typename... A>
@@ -354,6 +416,8 @@ __device__ __forceinline__ void spmm_process_item(
     bool active, int lane_in_group, int nt_mode, EP ep,
     const A *__restrict__... a) {
   constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
+  constexpr bool NORM = std::is_same_v<EP, AffineNormLane<T>>;
+  static_assert(!NORM || BETA == 0, "a launch that measures finishes its rows");
   using P = Prec<T>;
   using Staged = typename P::Staged;
   using Acc = typename P::Acc;  // products and partial sums
@@ -504,6 +568,15 @@ __device__ __forceinline__ void spmm_process_item(
           *reinterpret_cast<XV *>(cr) = P::template pack<VEC>(acc);
         } else {
           const XV packed = P::template pack<VEC>(acc);
+          if constexpr (NORM) {
+            // the value as stored (bf16: unpack what was packed) against the
+            // same 16 bytes of D[row]
+            const XV dv = ep.D ? *reinterpret_cast<const XV *>(
+                                     ep.D + (int64_t)row * k + col0)
+                               : XV{};
+            norm_add<Acc, VEC>(ep.sums, P::template unpack<VEC>(packed),
+                               P::template unpack<VEC>(dv));
+          }
           if (nt_mode) {
             constexpr int WORDS = P::template WORDS<VEC>;
             typedef typename P::Word nt_vec
@@ -524,6 +597,10 @@ __device__ __forceinline__ void spmm_process_item(
           if (rr) o = P::mad(ep.gamma, rr[j], o);
           if constexpr (BETA == 1) o += cr[j];
           cr[j] = o;
+          if constexpr (NORM) {
+            const Acc d = ep.D ? ep.D[(int64_t)row * k + col0 + j] : Acc(0);
+            norm_add<Acc, 1>(ep.sums, &o, &d);
+          }
         }
       }
     } else if constexpr (BETA == 1) {
@@ -647,6 +724,21 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_affine(
   SPMM_GRID_BODY(ep);
 }
 
+// The _affine_norm kernels: the same body once more, with the thread's two
+// sums behind the epilogue and the workgroup's reduction after the loop.
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_affine_norm(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end, int64_t n_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int xcd_remap,
+    int nt_mode, AffineNormEpilogue<T> ep) {
+  double sums[2] = {0.0, 0.0};
+  SPMM_GRID_BODY((AffineNormLane<T>{ep, sums}));
+  norm_block_reduce(sums[0], sums[1], ep.acc);
+}
+
 // Per-XCD queue scheduler. The static grid-stride schedule above interleaves
 // consecutive work items across all 8 XCDs and lets workgroups DRIFT apart
 // over millions of items, so the ~10 consumers of each 512-B X row (rows
@@ -719,6 +811,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q_affine(
   SPMM_Q_BODY(ep)
 }
 
+// A workgroup that found every queue dry still falls through to the
+// reduction: the body has no return.
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_q_affine_norm(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg, int32_t *__restrict__ qctr,
+    int chunk_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode,
+    AffineNormEpilogue<T> ep) {
+  double sums[2] = {0.0, 0.0};
+  SPMM_Q_BODY((AffineNormLane<T>{ep, sums}))
+  norm_block_reduce(sums[0], sums[1], ep.acc);
+}
+
 // Per-WAVE queue grab variant of spmm_kernel_q: each 64-lane wave pulls its
 // own chunk from the XCD's counter (lane-0 atomicAdd broadcast by wave
 // shuffle) — no __syncthreads per grab. Removes the whole-block rendezvous
@@ -777,6 +886,21 @@ __global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw_affine(
     T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode,
     AffineEpilogue<T> ep) {
   SPMM_QW_BODY(ep)
+}
+
+template <typename T, int VEC, int GROUP, int BETA, bool GUARD, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void spmm_kernel_qw_affine_norm(
+    const A *__restrict__... a,
+    const int32_t *__restrict__ item_row, const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end,
+    const int64_t *__restrict__ qseg, int32_t *__restrict__ qctr,
+    int chunk_items,
+    const T *__restrict__ X0, const T *__restrict__ X1,
+    T *__restrict__ C, int64_t k, int64_t col_off, int nt_mode,
+    AffineNormEpilogue<T> ep) {
+  double sums[2] = {0.0, 0.0};
+  SPMM_QW_BODY((AffineNormLane<T>{ep, sums}))
+  norm_block_reduce(sums[0], sums[1], ep.acc);
 }
 
 template <typename T>
@@ -872,6 +996,125 @@ __global__ void spmm_finalise_affine_bf16(uint16_t *__restrict__ C,
     *cp = bf16x8_pack(s);
     sp[0] = sp[1] = float4{0.f, 0.f, 0.f, 0.f};
   }
+}
+
+// spmm_finalise_affine_bf16 at beta = 0 that also measures the split rows it
+// finishes (the SpMM launches skipped them): the same arithmetic, written
+// out again because the kernel above is to stay the instructions it was.
+__global__ void spmm_finalise_affine_norm_bf16(
+    uint16_t *__restrict__ C, float *__restrict__ scratch,
+    const int32_t *__restrict__ rows, int64_t n_rows, int64_t k8,
+    const uint16_t *__restrict__ R, float alpha, float gamma,
+    const uint16_t *__restrict__ D, double *__restrict__ acc) {
+  const int64_t total = n_rows * k8;
+  double sums[2] = {0.0, 0.0};
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k8, j = t % k8;
+    float4 *sp = reinterpret_cast<float4 *>(scratch) + 2 * t;
+    const float4 s0 = sp[0], s1 = sp[1];
+    float s[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
+    const int64_t at = (int64_t)rows[i] * k8 + j;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) s[e] *= alpha;
+    if (R) {
+      const Float8 r = bf16x8_unpack(reinterpret_cast<const uint4 *>(R)[at]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s[e] = fmaf(gamma, r[e], s[e]);
+    }
+    const uint4 packed = bf16x8_pack(s);
+    const uint4 dv = D ? reinterpret_cast<const uint4 *>(D)[at] : uint4{};
+    norm_add<float, 8>(sums, bf16x8_unpack(packed), bf16x8_unpack(dv));
+    reinterpret_cast<uint4 *>(C)[at] = packed;
+    sp[0] = sp[1] = float4{0.f, 0.f, 0.f, 0.f};
+  }
+  norm_block_reduce(sums[0], sums[1], acc);
+}
+
+// fp32 / f64 split rows of a measuring call, once after its last column-tile
+// launch: the atomics have finished C[row], so read it back with D[row] over
+// all k columns and add. Launched with BLOCK_THREADS threads.
+template <typename T>
+__global__ void diffnorm_split_rows_kernel(const T *__restrict__ C,
+                                           const T *__restrict__ D,
+                                           const int32_t *__restrict__ rows,
+                                           int64_t n_rows, int64_t k,
+                                           double *__restrict__ acc) {
+  const int64_t total = n_rows * k;
+  double sums[2] = {0.0, 0.0};
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total;
+       t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / k, j = t % k;
+    const int64_t at = (int64_t)rows[i] * k + j;
+    const T c = C[at], d = D ? D[at] : T(0);
+    norm_add<T, 1>(sums, &c, &d);
+  }
+  norm_block_reduce(sums[0], sums[1], acc);
+}
+
+// The stand-alone form of the measure, over a contiguous n x k block: for
+// results that no single launch finishes. Shaped like axpby_rows_kernel
+// below (N elements = 16 bytes per thread when k allows, else one; D is null
+// for d = 0), launched with BLOCK_THREADS threads.
+template <typename T, int N>
+__global__ void diffnorm_rows_kernel(const T *__restrict__ C,
+                                     const T *__restrict__ D,
+                                     int64_t total_vec,
+                                     double *__restrict__ acc) {
+  using P = Prec<T>;
+  using Acc = typename P::Acc;
+  double sums[2] = {0.0, 0.0};
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+       t < total_vec; t += (int64_t)gridDim.x * blockDim.x) {
+    if constexpr (N == 1) {
+      const T c = C[t], d = D ? D[t] : T(0);
+      norm_add<Acc, 1>(sums, &c, &d);
+    } else {
+      using XV = typename P::template XV<N>;
+      const XV cv = reinterpret_cast<const XV *>(C)[t];
+      const XV dv = D ? reinterpret_cast<const XV *>(D)[t] : XV{};
+      norm_add<Acc, N>(sums, P::template unpack<N>(cv),
+                       P::template unpack<N>(dv));
+    }
+  }
+  norm_block_reduce(sums[0], sums[1], acc);
+}
+
+constexpr int NORM_MAX_BLOCKS = 4096;  // 2 atomics per workgroup
+
+template <typename T>
+int launch_diffnorm(const char *who, const T *C, const T *D, int64_t n,
+                    int64_t k, double *acc, hipStream_t stream) {
+  if (n < 0 || k <= 0 || (n > 0 && !C)) {
+    set_error(std::string(who) + ": bad arguments");
+    return -1;
+  }
+  if (!acc) {
+    set_error(std::string(who) + ": acc is NULL");
+    return -7;
+  }
+  if (D && D == C) {
+    set_error(std::string(who) + ": D must not be C");
+    return -8;
+  }
+  if (n == 0) return 0;
+  constexpr int N = 16 / sizeof(T);
+  const bool vec = (k % N == 0);
+  const int64_t total = vec ? n * (k / N) : n * k;
+  int blocks = (int)std::min<int64_t>(
+      (total + BLOCK_THREADS - 1) / BLOCK_THREADS, NORM_MAX_BLOCKS);
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(BLOCK_THREADS), 0, stream, C,
+                       D, total, acc);
+  };
+  if constexpr (sizeof(T) == 2) {  // bf16: the caller checked k % 8 == 0
+    launch(diffnorm_rows_kernel<T, N>);
+  } else {
+    if (vec) launch(diffnorm_rows_kernel<T, N>);
+    else     launch(diffnorm_rows_kernel<T, 1>);
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 // The stand-alone tail of the affine step, C = alpha * C + gamma * R over a
@@ -1216,31 +1459,37 @@ SpmmPlan spmm_plan(int64_t k, int64_t nnz, int queue_mode,
 }
 
 // a...: the structure's A-stream device pointers (Prec<T>::with_stream)
-// The entry symbol of a scheduler for the epilogue EP: the plain kernel or
-// its _affine form.
+// The entry symbol of a scheduler for the epilogue EP: the plain kernel, its
+// _affine form or its _affine_norm form.
 template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
           typename... A>
 constexpr auto grid_kernel() {
   if constexpr (std::is_same_v<EP, NoEpilogue>)
     return &spmm_kernel<T, VEC, GROUP, BETA, GUARD, A...>;
-  else
+  else if constexpr (std::is_same_v<EP, AffineEpilogue<T>>)
     return &spmm_kernel_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_affine_norm<T, VEC, GROUP, BETA, GUARD, A...>;
 }
 template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
           typename... A>
 constexpr auto q_kernel() {
   if constexpr (std::is_same_v<EP, NoEpilogue>)
     return &spmm_kernel_q<T, VEC, GROUP, BETA, GUARD, A...>;
-  else
+  else if constexpr (std::is_same_v<EP, AffineEpilogue<T>>)
     return &spmm_kernel_q_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_q_affine_norm<T, VEC, GROUP, BETA, GUARD, A...>;
 }
 template <typename EP, typename T, int VEC, int GROUP, int BETA, bool GUARD,
           typename... A>
 constexpr auto qw_kernel() {
   if constexpr (std::is_same_v<EP, NoEpilogue>)
     return &spmm_kernel_qw<T, VEC, GROUP, BETA, GUARD, A...>;
-  else
+  else if constexpr (std::is_same_v<EP, AffineEpilogue<T>>)
     return &spmm_kernel_qw_affine<T, VEC, GROUP, BETA, GUARD, A...>;
+  else
+    return &spmm_kernel_qw_affine_norm<T, VEC, GROUP, BETA, GUARD, A...>;
 }
 
 // ep: NoEpilogue{} for the plain entry points, else the affine step's
@@ -1249,6 +1498,7 @@ int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
                    const T *X1, T *C, int64_t k, int beta, hipStream_t stream,
                    const EP &ep, const A *... a) {
   constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
+  constexpr bool NORM = std::is_same_v<EP, AffineNormEpilogue<T>>;
   constexpr int GROUPS_PER_BLOCK = BLOCK_THREADS / GROUP;
   const int nt_mode = plan.nt_mode;
   const bool useq = plan.scheduler != SCHED_GRID_STRIDE;
@@ -1290,29 +1540,28 @@ int launch_spmm_vg(const CsrBlock &blk, const SpmmPlan &plan, const T *X0,
                            X0, X1, C, k, col_off, nt_mode);
       }
     };
-    if (useq) {
-      HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
-      if (qwave) {
-        if (beta == 0) {
-          if (guard) runq(qw_kernel<EP, T, VEC, GROUP, 0, true, A...>(), plan.chunk_items);
-          else       runq(qw_kernel<EP, T, VEC, GROUP, 0, false, A...>(), plan.chunk_items);
-        } else {
-          if (guard) runq(qw_kernel<EP, T, VEC, GROUP, 1, true, A...>(), plan.chunk_items);
-          else       runq(qw_kernel<EP, T, VEC, GROUP, 1, false, A...>(), plan.chunk_items);
-        }
-      } else if (beta == 0) {
-        if (guard) runq(q_kernel<EP, T, VEC, GROUP, 0, true, A...>(), plan.chunk_items);
-        else       runq(q_kernel<EP, T, VEC, GROUP, 0, false, A...>(), plan.chunk_items);
+    // the launch for a compile-time beta; the measuring kernels exist at
+    // beta = 0 only (their entry points refuse any other)
+    auto go = [&](auto beta_c) {
+      constexpr int BETA = decltype(beta_c)::value;
+      if (useq && qwave) {
+        if (guard) runq(qw_kernel<EP, T, VEC, GROUP, BETA, true, A...>(), plan.chunk_items);
+        else       runq(qw_kernel<EP, T, VEC, GROUP, BETA, false, A...>(), plan.chunk_items);
+      } else if (useq) {
+        if (guard) runq(q_kernel<EP, T, VEC, GROUP, BETA, true, A...>(), plan.chunk_items);
+        else       runq(q_kernel<EP, T, VEC, GROUP, BETA, false, A...>(), plan.chunk_items);
       } else {
-        if (guard) runq(q_kernel<EP, T, VEC, GROUP, 1, true, A...>(), plan.chunk_items);
-        else       runq(q_kernel<EP, T, VEC, GROUP, 1, false, A...>(), plan.chunk_items);
+        if (guard) run(grid_kernel<EP, T, VEC, GROUP, BETA, true, A...>());
+        else       run(grid_kernel<EP, T, VEC, GROUP, BETA, false, A...>());
       }
-    } else if (beta == 0) {
-      if (guard) run(grid_kernel<EP, T, VEC, GROUP, 0, true, A...>());
-      else       run(grid_kernel<EP, T, VEC, GROUP, 0, false, A...>());
+    };
+    if (useq)
+      HIP_CHECK(hipMemsetAsync(blk.qctr, 0, 8 * 32 * sizeof(int32_t), stream));
+    if constexpr (NORM) {
+      go(std::integral_constant<int, 0>{});
     } else {
-      if (guard) run(grid_kernel<EP, T, VEC, GROUP, 1, true, A...>());
-      else       run(grid_kernel<EP, T, VEC, GROUP, 1, false, A...>());
+      if (beta == 0) go(std::integral_constant<int, 0>{});
+      else           go(std::integral_constant<int, 1>{});
     }
     HIP_CHECK(hipGetLastError());
   }
@@ -1378,9 +1627,12 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
   using Other = Prec<std::conditional_t<P::dtype == 32, double, float>>;
   constexpr bool BF16 = std::is_same_v<T, uint16_t>;
   constexpr bool AFFINE = !std::is_same_v<EP, NoEpilogue>;
+  constexpr bool NORM = std::is_same_v<EP, AffineNormEpilogue<T>>;
   constexpr int plan_dtype = BF16 ? 16 : P::dtype;
   const std::string who =
-      std::string(AFFINE ? "arrow_spmm_affine" : "arrow_spmm") + P::suffix;
+      std::string(NORM ? "arrow_spmm_affine_norm"
+                       : AFFINE ? "arrow_spmm_affine" : "arrow_spmm") +
+      P::suffix;
   auto it = g_blocks.find(handle);
   if (it == g_blocks.end()) {
     set_error(who + ": bad handle");
@@ -1414,9 +1666,20 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
       set_error(who + ": R must not be C (X may alias R)");
       return -5;
     }
-    if (beta != 0 && beta != 1) {
-      set_error(who + ": beta must be 0 or 1, got " + std::to_string(beta));
+    if (NORM ? beta != 0 : (beta != 0 && beta != 1)) {
+      set_error(who + ": beta must be 0" + (NORM ? "" : " or 1") + ", got " +
+                std::to_string(beta));
       return -6;
+    }
+  }
+  if constexpr (NORM) {
+    if (!ep.acc) {
+      set_error(who + ": acc is NULL");
+      return -7;
+    }
+    if (ep.D && ep.D == C_dev) {
+      set_error(who + ": D must not be C (D may alias X or R)");
+      return -8;
     }
   }
   if constexpr (BF16) {
@@ -1477,13 +1740,29 @@ int spmm_dual_impl(int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,
                              ep.gamma);
         }
       };
-      if constexpr (AFFINE) {
+      if constexpr (NORM) {
+        hipLaunchKernelGGL(spmm_finalise_affine_norm_bf16, dim3(blocks),
+                           dim3(BLOCK_THREADS), 0, stream, C_dev,
+                           blk.bf16_scratch, blk.split_rows, blk.n_split_rows,
+                           k / 8, ep.R, ep.alpha, ep.gamma, ep.D, ep.acc);
+      } else if constexpr (AFFINE) {
         if (beta == 0) fin_affine(spmm_finalise_affine_bf16<0>);
         else           fin_affine(spmm_finalise_affine_bf16<1>);
       } else {
         if (beta == 0) fin(spmm_finalise_bf16<0>);
         else           fin(spmm_finalise_bf16<1>);
       }
+      HIP_CHECK(hipGetLastError());
+    }
+  } else if constexpr (NORM) {
+    // the split rows the launches skipped, now that their atomics are in
+    if (rc == 0 && blk.n_split_rows > 0) {
+      const int64_t total = blk.n_split_rows * k;
+      int blocks = (int)std::min<int64_t>(
+          (total + BLOCK_THREADS - 1) / BLOCK_THREADS, NORM_MAX_BLOCKS);
+      hipLaunchKernelGGL(diffnorm_split_rows_kernel<T>, dim3(blocks),
+                         dim3(BLOCK_THREADS), 0, stream, (const T *)C_dev,
+                         ep.D, blk.split_rows, blk.n_split_rows, k, ep.acc);
       HIP_CHECK(hipGetLastError());
     }
   }
@@ -1513,6 +1792,16 @@ int spmm_affine(int64_t handle, const T *X0, const T *X1, T *C, const T *R,
                 void *stream) {
   using Acc = typename Prec<T>::Acc;
   const AffineEpilogue<T> ep{R, (Acc)alpha, (Acc)gamma};
+  return spmm_dual_impl<T>(handle, X0, X1, C, k, beta, stream, ep, gamma);
+}
+
+// arrow_spmm*_affine_norm*: the affine step plus D and the accumulator pair
+template <typename T>
+int spmm_affine_norm(int64_t handle, const T *X0, const T *X1, T *C,
+                     const T *R, const T *D, double *acc, int64_t k,
+                     double alpha, double gamma, int beta, void *stream) {
+  using Acc = typename Prec<T>::Acc;
+  const AffineNormEpilogue<T> ep{R, (Acc)alpha, (Acc)gamma, D, acc};
   return spmm_dual_impl<T>(handle, X0, X1, C, k, beta, stream, ep, gamma);
 }
 
@@ -1943,6 +2232,49 @@ int arrow_axpby_rows_bf16(uint16_t *C_dev, const uint16_t *R_dev, int64_t n,
   if (!bf16_k_ok("arrow_axpby_rows_bf16", k)) return -3;
   return launch_axpby<uint16_t>("arrow_axpby_rows_bf16", C_dev, R_dev, n, k,
                                 alpha, gamma, (hipStream_t)stream);
+}
+
+// Step norms (ABI 1006): the affine step at beta = 0 that also adds
+// sum (c - d)^2 and sum c^2 over every row it writes into acc[0], acc[1].
+#define ARROW_AFFINE_NORM(sfx, T)                                             \
+  int arrow_spmm_dual_affine_norm##sfx(                                       \
+      int64_t handle, const T *X0_dev, const T *X1_dev, T *C_dev,             \
+      const T *R_dev, const T *D_dev, double *acc_dev, int64_t k,             \
+      double alpha, double gamma, int beta, void *stream) {                   \
+    return spmm_affine_norm<T>(handle, X0_dev, X1_dev, C_dev, R_dev, D_dev,   \
+                               acc_dev, k, alpha, gamma, beta, stream);       \
+  }                                                                           \
+  int arrow_spmm_affine_norm##sfx(                                            \
+      int64_t handle, const T *X_dev, T *C_dev, const T *R_dev,               \
+      const T *D_dev, double *acc_dev, int64_t k, double alpha, double gamma, \
+      int beta, void *stream) {                                               \
+    return spmm_affine_norm<T>(handle, X_dev, X_dev, C_dev, R_dev, D_dev,     \
+                               acc_dev, k, alpha, gamma, beta, stream);       \
+  }
+ARROW_AFFINE_NORM(, float)
+ARROW_AFFINE_NORM(_f64, double)
+ARROW_AFFINE_NORM(_bf16, uint16_t)
+#undef ARROW_AFFINE_NORM
+
+int arrow_diffnorm_rows_f32(const float *C_dev, const float *D_dev, int64_t n,
+                            int64_t k, double *acc_dev, void *stream) {
+  return launch_diffnorm<float>("arrow_diffnorm_rows_f32", C_dev, D_dev, n, k,
+                                acc_dev, (hipStream_t)stream);
+}
+
+int arrow_diffnorm_rows_f64(const double *C_dev, const double *D_dev,
+                            int64_t n, int64_t k, double *acc_dev,
+                            void *stream) {
+  return launch_diffnorm<double>("arrow_diffnorm_rows_f64", C_dev, D_dev, n,
+                                 k, acc_dev, (hipStream_t)stream);
+}
+
+int arrow_diffnorm_rows_bf16(const uint16_t *C_dev, const uint16_t *D_dev,
+                             int64_t n, int64_t k, double *acc_dev,
+                             void *stream) {
+  if (!bf16_k_ok("arrow_diffnorm_rows_bf16", k)) return -3;
+  return launch_diffnorm<uint16_t>("arrow_diffnorm_rows_bf16", C_dev, D_dev,
+                                   n, k, acc_dev, (hipStream_t)stream);
 }
 
 // bf16 routing: the pure copies move each row as k/2 floats through the fp32

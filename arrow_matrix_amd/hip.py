@@ -137,6 +137,26 @@ def _load():
                        ctypes.c_int64, ctypes.c_double, ctypes.c_double,
                        ctypes.c_void_p]
         fn.restype = ctypes.c_int
+    # step norms (ABI 1006): the affine lists with (D, acc) after R, and the
+    # stand-alone pass (C, D, n, k, acc, stream)
+    for sfx in ('', '_f64', '_bf16'):
+        fn = getattr(lib, 'arrow_spmm_affine_norm' + sfx)
+        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_int64, ctypes.c_double, ctypes.c_double,
+                       ctypes.c_int, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+        fn = getattr(lib, 'arrow_spmm_dual_affine_norm' + sfx)
+        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
+                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
+    for sfx in ('_f32', '_f64', '_bf16'):
+        fn = getattr(lib, 'arrow_diffnorm_rows' + sfx)
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
+        fn.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -243,12 +263,20 @@ class CsrBlockGPU:
 
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0,
              feat_dtype=None, alpha: float = 1.0, gamma: float = 0.0,
-             R_ptr: int = 0):
+             R_ptr: int = 0, norm=None):
         """C (+)= A @ X on device pointers (e.g. torch tensor data_ptr()).
         With alpha, gamma or R_ptr given: the fused affine step
         C = alpha * (A @ X) + gamma * R + beta * C (arrow_spmm_affine*;
         R_ptr 0 needs gamma 0). Without them the plain entry point is
-        called, as before."""
+        called, as before. norm=(D_ptr, acc_ptr): the step also adds
+        sum (C - D)^2 and sum C^2 into the two device doubles at acc_ptr
+        (arrow_spmm_affine_norm*; beta 0 only, D_ptr 0 means D = 0)."""
+        if norm is not None:
+            fn, name = self._entry('arrow_spmm_affine_norm', feat_dtype)
+            _check(fn(self._handle, X_ptr, C_ptr, R_ptr or None,
+                      norm[0] or None, norm[1] or None, k, float(alpha),
+                      float(gamma), beta, stream), name)
+            return
         if self._is_affine(alpha, gamma, R_ptr):
             fn, name = self._entry('arrow_spmm_affine', feat_dtype)
             _check(fn(self._handle, X_ptr, C_ptr, R_ptr or None, k,
@@ -273,10 +301,18 @@ class CsrBlockGPU:
 
     def spmm_dual(self, X0_ptr: int, X1_ptr: int, C_ptr: int, k: int,
                   beta: int, stream: int = 0, feat_dtype=None,
-                  alpha: float = 1.0, gamma: float = 0.0, R_ptr: int = 0):
+                  alpha: float = 1.0, gamma: float = 0.0, R_ptr: int = 0,
+                  norm=None):
         """Fused dual-operand SpMM: negative column indices (encoded at
-        upload as -(idx+1)) read X1 (see include/arrow_spmm.h). alpha, gamma
-        and R_ptr as in spmm (arrow_spmm_dual_affine*)."""
+        upload as -(idx+1)) read X1 (see include/arrow_spmm.h). alpha, gamma,
+        R_ptr and norm as in spmm (arrow_spmm_dual_affine*,
+        arrow_spmm_dual_affine_norm*)."""
+        if norm is not None:
+            fn, name = self._entry('arrow_spmm_dual_affine_norm', feat_dtype)
+            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, R_ptr or None,
+                      norm[0] or None, norm[1] or None, k, float(alpha),
+                      float(gamma), beta, stream), name)
+            return
         if self._is_affine(alpha, gamma, R_ptr):
             fn, name = self._entry('arrow_spmm_dual_affine', feat_dtype)
             _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, R_ptr or None, k,
@@ -343,6 +379,15 @@ def axpby_rows(C_ptr: int, R_ptr: int, n: int, k: int, alpha: float,
     fn, name = _route('axpby_rows', dtype)
     _check(fn(C_ptr, R_ptr or None, n, k, float(alpha), float(gamma), stream),
            name)
+
+
+def diffnorm_rows(C_ptr: int, D_ptr: int, n: int, k: int, acc_ptr: int,
+                  stream: int = 0, dtype=np.float32):
+    """acc[0] += sum (C - D)^2, acc[1] += sum C^2 over n contiguous rows of
+    width k (the stand-alone step norms; D_ptr 0 means D = 0; acc_ptr is two
+    device doubles the caller zeroed)."""
+    fn, name = _route('diffnorm_rows', dtype)
+    _check(fn(C_ptr, D_ptr or None, n, k, acc_ptr or None, stream), name)
 
 
 PLAN_FIELDS = ('vec', 'group', 'scheduler', 'nt_mode', 'chunk_items',

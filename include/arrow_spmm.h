@@ -364,6 +364,84 @@ int arrow_axpby_rows_bf16(uint16_t *C_dev, const uint16_t *R_dev, int64_t n,
                           int64_t k, double alpha, double gamma,
                           void *stream);
 
+/* ---------------------------------------------------------------------
+ * Step norms (ABI 1006). The workloads of the affine step run until the
+ * iterate stops moving, so the same launches can also measure the step:
+ *
+ *     acc[0] += sum (c - d)^2        acc[1] += sum c^2
+ *
+ * over every element of every output row the structure writes (after
+ * row_ids, empty rows included, columns 0..k-1). c is the value AS STORED in
+ * C (bf16: after the single rounding), d the stored value of D[row]. D is a
+ * row-major matrix of the feature type, shaped like C and indexed by OUTPUT
+ * row exactly as R is; D == NULL means d = 0. c - d is formed in the
+ * accumulator type (float for fp32 and bf16 features, double for float64);
+ * both squares and all summation are double in every precision.
+ *
+ * acc points at two doubles in device memory. The call ADDS into them: the
+ * caller zeroes them, so several launches can share one pair. Non-split rows
+ * are measured in the write-back of the launch that computes them (one more
+ * row read, no extra pass); each workgroup reduces its lanes' sums and adds
+ * them with one float64 atomic per accumulator. Split hub rows are measured
+ * once per call after the last column tile: fp32 / f64 by a small pass over
+ * the split-row table, bf16 in the finalise pass that writes them.
+ *
+ * Rules, in addition to the affine step's (which carry over unchanged); a
+ * broken one returns a negative code, sets arrow_last_error(), launches
+ * nothing and leaves C and acc untouched:
+ *   - beta other than 0 is refused: a launch that does not finish its rows
+ *     has no business measuring them;
+ *   - acc == NULL is refused;
+ *   - D == C is refused. D may alias X or R.
+ *
+ * C is what the affine entry point writes, bit for bit, in every precision;
+ * (alpha, gamma, R) = (1, 0, NULL) writes the plain product bit for bit.
+ * The launch plan is the plain one (arrow_spmm_plan / _f64 / _bf16).
+ * ------------------------------------------------------------------- */
+int arrow_spmm_affine_norm(int64_t handle, const float *X_dev, float *C_dev,
+                           const float *R_dev, const float *D_dev,
+                           double *acc_dev, int64_t k, double alpha,
+                           double gamma, int beta, void *stream);
+int arrow_spmm_dual_affine_norm(int64_t handle, const float *X0_dev,
+                                const float *X1_dev, float *C_dev,
+                                const float *R_dev, const float *D_dev,
+                                double *acc_dev, int64_t k, double alpha,
+                                double gamma, int beta, void *stream);
+int arrow_spmm_affine_norm_f64(int64_t handle, const double *X_dev,
+                               double *C_dev, const double *R_dev,
+                               const double *D_dev, double *acc_dev,
+                               int64_t k, double alpha, double gamma,
+                               int beta, void *stream);
+int arrow_spmm_dual_affine_norm_f64(int64_t handle, const double *X0_dev,
+                                    const double *X1_dev, double *C_dev,
+                                    const double *R_dev, const double *D_dev,
+                                    double *acc_dev, int64_t k, double alpha,
+                                    double gamma, int beta, void *stream);
+int arrow_spmm_affine_norm_bf16(int64_t handle, const uint16_t *X_dev,
+                                uint16_t *C_dev, const uint16_t *R_dev,
+                                const uint16_t *D_dev, double *acc_dev,
+                                int64_t k, double alpha, double gamma,
+                                int beta, void *stream);
+int arrow_spmm_dual_affine_norm_bf16(int64_t handle, const uint16_t *X0_dev,
+                                     const uint16_t *X1_dev, uint16_t *C_dev,
+                                     const uint16_t *R_dev,
+                                     const uint16_t *D_dev, double *acc_dev,
+                                     int64_t k, double alpha, double gamma,
+                                     int beta, void *stream);
+
+/* The stand-alone form of the measure, for results that no single launch
+ * finishes: the same two sums over n contiguous rows of width k (device,
+ * row-major), added into acc. bf16 needs k % 8 == 0. D == NULL means d = 0;
+ * acc == NULL and D == C are refused; n == 0 is a no-op. */
+int arrow_diffnorm_rows_f32(const float *C_dev, const float *D_dev, int64_t n,
+                            int64_t k, double *acc_dev, void *stream);
+int arrow_diffnorm_rows_f64(const double *C_dev, const double *D_dev,
+                            int64_t n, int64_t k, double *acc_dev,
+                            void *stream);
+int arrow_diffnorm_rows_bf16(const uint16_t *C_dev, const uint16_t *D_dev,
+                             int64_t n, int64_t k, double *acc_dev,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif

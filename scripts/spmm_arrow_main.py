@@ -47,11 +47,22 @@ def main() -> None:
                              'features X0 as residual (default: off, plain '
                              'X <- A@X on fresh features)')
 
+    parser.add_argument('--tol', type=float, default=None, metavar='T',
+                        help='with --damping: stop after the first iteration '
+                             'whose relative step ||X_new - X_old|| / '
+                             '||X_new|| is <= T, and print the steps taken '
+                             '(default: off, all -z iterations run)')
+
     args = vars(parser.parse_args())
-    # off: the printed arguments and the run are what they were without it
+    # off: the printed arguments and the run are what they were without them
     damping = args.pop('damping')
+    tol = args.pop('tol')
+    if tol is not None and damping is None:
+        parser.error('--tol needs --damping')
     if damping is not None:
         args['damping'] = damping
+    if tol is not None:
+        args['tol'] = tol
     comm = default_comm()
     utils.mpi_print(comm.rank, str(args))
 
@@ -73,7 +84,8 @@ def main() -> None:
                            slim=args['slim'],
                            npy_format=args['npy'],
                            **({} if damping is None
-                              else {'damping': damping}))
+                              else {'damping': damping}),
+                           **({} if tol is None else {'tol': tol}))
 
 
 if __name__ == '__main__':
