@@ -1845,6 +1845,27 @@ static int64_t csr_create_impl(int64_t rows, int64_t cols, int64_t nnz,
     set_error("arrow_csr_create: nnz exceeds int32 (per-block limit)");
     return -1;
   }
+  // rows, columns and output row ids travel as int32 (the work items keep
+  // bit 31 of the row for the split flag): refuse what does not fit, before
+  // anything is allocated
+  if (rows > INT32_MAX || cols > INT32_MAX) {
+    set_error("arrow_csr_create: " +
+              std::string(rows > INT32_MAX ? "rows " : "cols ") +
+              std::to_string(rows > INT32_MAX ? rows : cols) +
+              " exceeds int32 (per-block limit)");
+    return -1;
+  }
+  if (row_ids) {
+    for (int64_t r = 0; r < rows; ++r) {
+      if (row_ids[r] < 0 || row_ids[r] > INT32_MAX) {
+        set_error("arrow_csr_create: row id " + std::to_string(row_ids[r]) +
+                  " at row " + std::to_string(r) +
+                  (row_ids[r] < 0 ? " is negative (output row ids are int32)"
+                                  : " exceeds int32"));
+        return -1;
+      }
+    }
+  }
   CsrBlock blk;
   blk.rows = rows;
   blk.cols = cols;

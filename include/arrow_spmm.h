@@ -48,7 +48,16 @@ int arrow_abi_version(void);
 
 /* Upload a CSR block (host arrays) once; returns a handle >= 0, < 0 on
  * error. indptr has rows+1 int64 entries; indices int32; data fp32.
- * Builds the row-segment work list for the SpMM kernel at upload time. */
+ * Builds the row-segment work list for the SpMM kernel at upload time.
+ *
+ * Limits of one structure, for every arrow_csr_create* entry point: nnz,
+ * rows, cols (hence every column index, of either sign) and every output row
+ * id of row_ids fit int32, and a row id is not negative; anything else is
+ * refused with -1 before anything is allocated, and the message names the
+ * limit and the offending value (e.g. "arrow_csr_create: row id 2147483648
+ * at row 7 exceeds int32"). Element and byte offsets into X, C, R and D
+ * (row * k + column) are 64-bit everywhere, so rows * k and cols * k may
+ * pass 2^31 elements and 4 GiB. */
 int64_t arrow_csr_create(int64_t rows, int64_t cols, int64_t nnz,
                          const int64_t *indptr, const int32_t *indices,
                          const float *data);
