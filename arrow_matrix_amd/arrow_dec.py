@@ -22,17 +22,20 @@ MI355X-first deviations:
   * The loader reads the decomposition on every rank (one node, shared
     filesystem, mmap) instead of root-scatter over MPI.
 """
+import os
+import sys
+import time
+import warnings
 from typing import List, Optional
 
 import numpy as np
-
+import torch
 
 from . import graphio, hip, tables
 from .arrow_matrix import ArrowMatrix
-from .arrow_slim import ArrowSlimMPI
+from .arrow_slim import AffineStep, ArrowSlimMPI
 from .comm import Comm, default_comm
 from .common import wb_logging
-import time
 
 
 class _Exchange:
@@ -73,8 +76,8 @@ class ArrowDecompositionMPI:
         # R_i[r] (-1 = unmapped).
         self._folded: Optional[List] = None
         self._fold_maps: Optional[List] = None
-        # affine step (set_affine_step): part 0's (alpha, gamma, R) or None
-        self._affine = None
+        # affine step (set_affine_step): part 0's AffineStep or None
+        self._affine: Optional[AffineStep] = None
         # step norms (track_step_norms): at L == 1 part 0's engine measures
         # its own step; at L > 1 this accumulator takes one stand-alone pass
         # over part 0's finished result
@@ -202,7 +205,6 @@ class ArrowDecompositionMPI:
         cover every referenced row (the exchange would read rows no sender
         wrote)."""
         assert len(blocked) == self.decomposition_length
-        import os
         # ARROW_FOLD: '0' sequential exchange, '1' full fold, '2' row fold
         # (backward cascade only), 'auto' (default): full fold in the
         # launch-bound / memory-pressure regimes, row fold otherwise at
@@ -227,12 +229,9 @@ class ArrowDecompositionMPI:
                 # 0's buffers): e.g. L=2 at 100M rows x k=128 needs ~260
                 # GB sequentially but ~175 GB folded
                 try:
-                    import torch as _t
-                    free, total = _t.cuda.mem_get_info()
+                    free, total = torch.cuda.mem_get_info()
                     k = self._n_feature_columns
-                    be0 = self.engines[0].backend
-                    itemsize = getattr(be0, 'feat_itemsize',
-                                       self.engines[0].np_dtype.itemsize)
+                    itemsize = self.engines[0].backend.feat_itemsize
                     need = [itemsize * k * (2 * eng.n_owned * self.width
                                      + 2 * self.width)
                             for eng in self.engines]
@@ -254,11 +253,10 @@ class ArrowDecompositionMPI:
                              and self.device == 'gpu' and not auto_fold))
         want_fold = foldable and (fold_env == '1' or auto_fold)
         if os.environ.get('ARROW_FOLD_DEBUG') == '1':
-            import sys as _sys
             print(f"# fold decision: full={want_fold} row={want_row_fold} "
                   f"auto={auto_fold} env={fold_env} "
                   f"maps={self._fold_maps is not None} "
-                  f"P={self.comm.size} L={len(blocked)}", file=_sys.stderr)
+                  f"P={self.comm.size} L={len(blocked)}", file=sys.stderr)
         if want_fold:
             self.engines[0].load_sparse_matrix_from_blocks(blocked[0])
             folded, dropped = self._build_folded(blocked, fold_cols=True)
@@ -266,7 +264,6 @@ class ArrowDecompositionMPI:
                 self._folded = folded
                 self._fold_cols = True
                 return
-            import warnings
             warnings.warn(
                 f"ARROW_FOLD: {dropped} entries reference rows outside the "
                 f"composed permutation chain; falling back to the "
@@ -404,9 +401,11 @@ class ArrowDecompositionMPI:
         self.engines[0].clear_affine_step()
 
     def _affine_inside(self) -> bool:
-        """True when part 0's own spmm() (and the folded launches) carry the
-        affine step; False when step() runs the plain step and then the
-        tail on part 0's aggregated result."""
+        """Who finishes the affine step of the decomposition, decided here
+        alone: True when part 0's own step (ArrowSlimMPI._spmm_step, which
+        asks its _launch_finishes_step) and the folded launches carry it;
+        False when step() runs the plain step and then the tail on part 0's
+        aggregated result."""
         if self.decomposition_length == 1:
             return True
         return (self._folded is not None
@@ -488,21 +487,28 @@ class ArrowDecompositionMPI:
         eng0.backend.diffnorm_rows(eng0.C_i, X_pre, self._norm_acc)
 
     def _step_affine(self) -> None:
+        """The step with what _affine_inside() decided handed down as an
+        argument: part 0's engine state is read, never written."""
         if self._affine is None:
-            self._step_plain()
-            return
-        eng0 = self.engines[0]
-        inside = self._affine_inside()
-        eng0._affine = self._affine if inside else None
-        try:
-            self._step_plain()
-        finally:
-            eng0._affine = self._affine
-        if not inside:
-            eng0._affine_tail()
+            # part 0 applies whatever was set on its engine directly
+            self._step_plain(self.engines[0]._affine)
+        elif self._affine_inside():
+            self._step_plain(self._affine)
+        else:
+            self._step_plain(None)
+            self.engines[0]._affine_tail(self._affine)
 
-    def _step_plain(self) -> None:
-        """One X <- A @ X iteration (reference arrow_dec_mpi.py:283-307).
+    def _spmm_part(self, i: int, affine: Optional[AffineStep]) -> None:
+        """Part i's arrow SpMM; part 0 applies `affine` (None: plain)."""
+        eng = self.engines[i]
+        if i == 0:
+            eng._spmm_step(affine, eng._norm_acc)
+        else:
+            eng.spmm()
+
+    def _step_plain(self, affine: Optional[AffineStep] = None) -> None:
+        """One X <- A @ X iteration (reference arrow_dec_mpi.py:283-307), or
+        with `affine` the affine step inside part 0's launches.
         At world>1 with L>1 the forward exchange for pair (i, i+1) is
         POSTED asynchronously and part i's SpMM runs while the transfer is
         in flight — the reference's own overlap (the Ialltoallv posted at
@@ -510,26 +516,26 @@ class ArrowDecompositionMPI:
         :306). Data dependencies (and results) are identical to the
         sequential schedule."""
         if self._folded is not None:
-            self._step_folded()
+            self._step_folded(affine)
             return
         if self.comm.size > 1 and self.decomposition_length > 1:
             tic = time.perf_counter()
-            self._step_overlapped_forward()
+            self._step_overlapped_forward(affine)
             wb_logging.log({'spmm_arrow_time': time.perf_counter() - tic})
         else:
             tic = time.perf_counter()
             self._propagate_features()
             wb_logging.log({"spmm_bcast_time": time.perf_counter() - tic})
             tic = time.perf_counter()
-            for eng in self.engines:
-                eng.spmm()
+            for i in range(self.decomposition_length):
+                self._spmm_part(i, affine)
             wb_logging.log({'spmm_arrow_time': time.perf_counter() - tic})
 
         tic = time.perf_counter()
         self._aggregate()
         wb_logging.log({"spmm_reduce_time": time.perf_counter() - tic})
 
-    def _step_overlapped_forward(self) -> None:
+    def _step_overlapped_forward(self, affine=None) -> None:
         """Forward exchange posted async, overlapped with the previous
         part's SpMM (world>1). Same dependency chain as
         _propagate_features + the spmm loop: exchange i reads part i's
@@ -555,9 +561,9 @@ class ArrowDecompositionMPI:
                 recvbuf, works = self.comm.alltoallv_async(
                     sendbuf, ex.send_counts, ex.recv_counts)
                 pending = (ex, recvbuf, works)
-            self.engines[i].spmm()
+            self._spmm_part(i, affine)
 
-    def _step_folded(self) -> None:
+    def _step_folded(self, affine: Optional[AffineStep] = None) -> None:
         """Folded iteration: part 0's arrow SpMM, then each folded part as
         one beta=1 SpMM accumulating into part 0's fresh C — results
         identical to the sequential propagate/spmm/aggregate cascade (same
@@ -568,14 +574,14 @@ class ArrowDecompositionMPI:
         eng0 = self.engines[0]
         # affine step: part 0's launch carried alpha and gamma * R, the
         # folded beta=1 launches carry alpha only
-        alpha = eng0._affine[0] if eng0._affine is not None else 1.0
+        alpha = affine.alpha if affine is not None else 1.0
         if not self._fold_cols:
             tic = time.perf_counter()
             self._propagate_features()
             wb_logging.log({"spmm_bcast_time": time.perf_counter() - tic})
         X_pre = eng0.feature_tile()
         tic = time.perf_counter()
-        eng0.spmm()
+        self._spmm_part(0, affine)
         for i, h in enumerate(self._folded, start=1):
             X_op = X_pre if self._fold_cols \
                 else self.engines[i].feature_tile()

@@ -22,7 +22,9 @@ MI355X-first deviations from the reference:
     arrow_mpi.py:314).
   * Collectives are RCCL over xGMI (comm.py) instead of mpi4py.
 """
-from typing import List, Optional
+import os
+import time
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -32,7 +34,14 @@ from .arrow_matrix import ArrowMatrix
 from .backends import make_backend
 from .comm import Comm
 from .common import wb_logging
-import time
+
+
+class AffineStep(NamedTuple):
+    """The step X <- alpha * A@X + gamma * R; R is the engine's own residual
+    buffer, or None at gamma == 0."""
+    alpha: float = 1.0
+    gamma: float = 0.0
+    R: Optional[torch.Tensor] = None
 
 
 class ArrowSlimMPI(ArrowMatrix):
@@ -115,9 +124,9 @@ class ArrowSlimMPI(ArrowMatrix):
         # (start_event, end_event, nnz, c_rows, x_rows) tuples)
         self.kernel_events: Optional[list] = None
         # affine step X <- alpha*A@X + gamma*R (set_affine_step): None, or
-        # (alpha, gamma, R) with R the engine's own residual buffer (or None
+        # an AffineStep whose R is the engine's own residual buffer (or None
         # at gamma == 0); never swapped with X / C
-        self._affine = None
+        self._affine: Optional[AffineStep] = None
         self._R: Optional[torch.Tensor] = None
         # step norms (track_step_norms): None, or the backend's two-double
         # accumulator {sum (C - X)^2, sum C^2} of the last spmm()
@@ -200,9 +209,8 @@ class ArrowSlimMPI(ArrowMatrix):
         """Chunk count of the C_0 (all)reduce pipeline — a pure function of
         (width, world size) so every rank issues the identical collective
         schedule, including ranks that own no blocks of this matrix."""
-        import os as _os
         n_chunks = 4 if (w >= 64 and self.comm.size > 1) else 1
-        env_c = _os.environ.get('ARROW_ROW0_CHUNKS')
+        env_c = os.environ.get('ARROW_ROW0_CHUNKS')
         if env_c:
             n_chunks = max(1, min(int(env_c), w))
         return n_chunks
@@ -215,8 +223,7 @@ class ArrowSlimMPI(ArrowMatrix):
         X), 2 column sort WITHIN each nnz-balanced row segment (two-level:
         each XCD keeps its contiguous C_0 range but walks its X gathers in
         column order)."""
-        import os as _os
-        v = _os.environ.get('ARROW_ROW0_COLSORT', '0')
+        v = os.environ.get('ARROW_ROW0_COLSORT', '0')
         return int(v) if v in ('0', '1', '2') else 0
 
     def _build_merged_gpu(self) -> None:
@@ -234,8 +241,7 @@ class ArrowSlimMPI(ArrowMatrix):
         # scheduler): measured +12% at 100M (4435 vs 3966 GF/s) and +22%
         # at 20M (gpurun_out/r02_ab.log). ARROW_FUSE_ALL=0 restores the
         # two-launch layout (required by ARROW_SPLIT_COL/ARROW_PAR_ROW0).
-        import os as _os
-        fuse_all = (_os.environ.get('ARROW_FUSE_ALL', '1') != '0'
+        fuse_all = (os.environ.get('ARROW_FUSE_ALL', '1') != '0'
                     and self.comm.size == 1 and self.first_block == 0
                     and self.n_owned == self.tiles_per_side)
         # --- row-0 merge: C_0 = [A_0,first .. A_0,last-1] @ X_stripe -------
@@ -262,7 +268,7 @@ class ArrowSlimMPI(ArrowMatrix):
             data = np.concatenate(data_cat)
             bounds = [w * q // n_chunks for q in range(n_chunks + 1)]
             self._A_row0 = []
-            qb_row0 = int(_os.environ.get('ARROW_Q_BLOCKS_ROW0', '0'))
+            qb_row0 = int(os.environ.get('ARROW_Q_BLOCKS_ROW0', '0'))
             for q in range(n_chunks):
                 lo, hi = bounds[q], bounds[q + 1]
                 m = (rows >= lo) & (rows < hi)
@@ -291,7 +297,7 @@ class ArrowSlimMPI(ArrowMatrix):
         # order is sorted by hub column — the zipf-skewed X_0 gather then
         # walks the hot head near-sequentially (cache-friendly) at the cost
         # of one extra C read-modify-write pass
-        split_col = (_os.environ.get('ARROW_SPLIT_COL', '0') == '1'
+        split_col = (os.environ.get('ARROW_SPLIT_COL', '0') == '1'
                      and not fuse_all)
         col_rows, col_cols, col_data = [], [], []
         n_rest = 0
@@ -338,11 +344,11 @@ class ArrowSlimMPI(ArrowMatrix):
             # Auto-split into row-range chunks when the merged nonzero count
             # would overflow the per-structure int32 limit (scale headroom
             # beyond cfg4); ARROW_REST_CHUNK_NNZ forces small chunks in tests.
-            cap = int(_os.environ.get('ARROW_REST_CHUNK_NNZ', 1 << 30))
+            cap = int(os.environ.get('ARROW_REST_CHUNK_NNZ', 1 << 30))
             self._A_rest = self._merged_chunks(rest_rows, nw * w, rows_cat,
                                                cols_cat, data_cat,
                                                x_rows_total, cap)
-            qb_rest = int(_os.environ.get('ARROW_Q_BLOCKS_REST', '0'))
+            qb_rest = int(os.environ.get('ARROW_Q_BLOCKS_REST', '0'))
             if qb_rest:
                 for h, _, _ in self._A_rest:
                     h.set_qblocks(qb_rest)
@@ -481,7 +487,6 @@ class ArrowSlimMPI(ArrowMatrix):
             # capacity but the guard is not). Only bytes that would be
             # NEWLY allocated count (a repeated zero_rhs with matching
             # shapes reuses the buffers).
-            import torch as _t
             w_, k_ = number_of_rows_per_rank, number_of_columns
             stripe_sh = (max(self.n_owned, 1) * w_, k_)
             shapes = [('C_i', stripe_sh), ('X_i', stripe_sh),
@@ -564,7 +569,7 @@ class ArrowSlimMPI(ArrowMatrix):
         if gamma != 0.0 and residual is None:
             raise ValueError("set_affine_step: gamma != 0 needs a residual")
         if residual is None:
-            self._affine = (alpha, gamma, None)
+            self._affine = AffineStep(alpha, gamma, None)
             return
         if self.C_i is None:
             raise ValueError("set_affine_step: call zero_rhs first (the "
@@ -574,7 +579,7 @@ class ArrowSlimMPI(ArrowMatrix):
             raise ValueError(
                 f"set_affine_step: residual has shape "
                 f"{tuple(residual.shape)}, the feature stripe {shape}")
-        bf16 = getattr(self.backend, 'bf16', False)
+        bf16 = self.backend.bf16
         if isinstance(residual, torch.Tensor):
             ok = residual.dtype == self.backend.torch_dtype or \
                 (bf16 and residual.dtype == torch.float32)
@@ -591,18 +596,17 @@ class ArrowSlimMPI(ArrowMatrix):
         if self._R is None or tuple(self._R.shape) != shape:
             self._R = self.backend.zeros(shape)
         self._R.copy_(self.backend.asarray(residual))
-        self._affine = (alpha, gamma, self._R)
+        self._affine = AffineStep(alpha, gamma, self._R)
 
     def clear_affine_step(self) -> None:
         """Back to the plain step X <- A@X; the residual buffer is freed."""
         self._affine = None
         self._R = None
 
-    def _affine_tail(self) -> None:
+    def _affine_tail(self, affine: AffineStep) -> None:
         """C = alpha * C + gamma * R on this rank's finished result: the
         layouts whose result no single launch finishes."""
-        alpha, gamma, R = self._affine
-        self.backend.axpby_rows(self.C_i, R, alpha, gamma)
+        self.backend.axpby_rows(self.C_i, affine.R, affine.alpha, affine.gamma)
         # a cached X_0 (the allreduce_x0 fast path) holds the plain C_0
         self._x0_valid = False
 
@@ -633,10 +637,10 @@ class ArrowSlimMPI(ArrowMatrix):
         d2, c2 = self._norm_acc.tolist()
         return float(np.sqrt(d2)), float(np.sqrt(c2))
 
-    def _measure_result(self) -> None:
+    def _measure_result(self, norm_acc) -> None:
         """The stand-alone pass: the layouts whose result no single launch
         finishes (and the cpu device)."""
-        self.backend.diffnorm_rows(self.C_i, self.X_i, self._norm_acc)
+        self.backend.diffnorm_rows(self.C_i, self.X_i, norm_acc)
 
     def _select_result_buffer(self):
         if self.X_i is None or self.C_i.data_ptr() != self.X_i.data_ptr():
@@ -652,7 +656,7 @@ class ArrowSlimMPI(ArrowMatrix):
         """Stores a reference (no copy) when X already lives on this
         engine's device; otherwise moves it there once."""
         assert X is not None
-        bf16 = getattr(self.backend, 'bf16', False)
+        bf16 = self.backend.bf16
         if isinstance(X, torch.Tensor) and (X.device.type == self.backend.device
                                             or (self.backend.device == 'cuda' and X.is_cuda)) \
                 and not (bf16 and X.dtype != torch.bfloat16):
@@ -687,10 +691,25 @@ class ArrowSlimMPI(ArrowMatrix):
         if device is not None and device != self.device:
             raise ValueError(
                 f"engine was built for device={self.device!r}; got {device!r}")
+        self._spmm_step(self._affine, self._norm_acc)
+
+    @property
+    def _launch_finishes_step(self) -> bool:
+        """True when the engine's own launch applies the affine step and
+        measures the step norms in its write-back (the GPU single-launch
+        layout); otherwise _spmm_step runs the tail kernel and the
+        stand-alone pass on the finished result. The one place that decides
+        it for this engine."""
+        return self.backend.device == 'cuda' and self._A_all is not None
+
+    def _spmm_step(self, affine: Optional[AffineStep], norm_acc) -> None:
+        """spmm() with the affine step to apply (None: the plain step) and
+        the accumulator to measure into (None: no measure) as arguments:
+        ArrowDecompositionMPI passes what it decided for part 0."""
         self._select_result_buffer()
         w = self.width
-        if self._norm_acc is not None:
-            self._norm_acc.zero_()  # on the launch stream
+        if norm_acc is not None:
+            norm_acc.zero_()  # on the launch stream
 
         # X_0 broadcast (arrow_slim_mpi.py:265-273); owner of block 0 is
         # rank 0. Overlapped: the row-0 launch below reads only the stripe,
@@ -718,7 +737,7 @@ class ArrowSlimMPI(ArrowMatrix):
 
         tic = time.perf_counter()
         if self.backend.device == 'cuda':
-            self._spmm_gpu(bcast_work)
+            self._spmm_gpu(bcast_work, affine, norm_acc)
         else:
             if bcast_work is not None:
                 bcast_work.wait()
@@ -743,12 +762,11 @@ class ArrowSlimMPI(ArrowMatrix):
             self.X_0, self.C_0 = self.C_0, self.X_0
             self._x0_valid = True
             self._prev_result = self.C_i
-        if self._affine is not None and not (
-                self.backend.device == 'cuda' and self._A_all is not None):
-            self._affine_tail()
-        if self._norm_acc is not None and not (
-                self.backend.device == 'cuda' and self._A_all is not None):
-            self._measure_result()
+        if not self._launch_finishes_step:
+            if affine is not None:
+                self._affine_tail(affine)
+            if norm_acc is not None:
+                self._measure_result(norm_acc)
 
     def _timed(self, fn, nnz, c_rows, x_rows):
         """HIP-event instrumentation for the roofline (bench.py)."""
@@ -762,7 +780,8 @@ class ArrowSlimMPI(ArrowMatrix):
         e.record()
         self.kernel_events.append((s, e, nnz, c_rows, x_rows))
 
-    def _spmm_gpu(self, bcast_work=None) -> None:
+    def _spmm_gpu(self, bcast_work=None, affine: Optional[AffineStep] = None,
+                  norm_acc=None) -> None:
         """Two fused launches on the resident merged structures
         (DESIGN.md §kernels), with the X_0 broadcast and the C_0 reduce
         overlapped with compute (RCCL runs on its own stream; `wait()`
@@ -787,26 +806,16 @@ class ArrowSlimMPI(ArrowMatrix):
 
         if self._A_all is not None:
             # single process: whole matrix in ONE fused launch, C in place;
-            # X_0 == X_i[:w] so the second operand is the stripe itself
+            # X_0 == X_i[:w] so the second operand is the stripe itself.
+            # This launch finishes the step (_launch_finishes_step): the
+            # affine step rides in its write-back, and it measures every row
+            # of C_i against the features it read, with or without one
             h = self._A_all
-            if self._norm_acc is not None:
-                # the launch writes every row of C_i and measures each against
-                # the features it read, with or without an affine step
-                alpha, gamma, R = self._affine or (1.0, 0.0, None)
-                norm = (self.X_i, self._norm_acc)
-                self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i,
-                                                 self.C_i, 0, alpha, gamma, R,
-                                                 norm=norm),
-                            h.nnz, self.n_owned * w, h.x_rows)
-                return
-            if self._affine is not None:
-                # the affine step rides in this launch's write-back
-                alpha, gamma, R = self._affine
-                self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i,
-                                                 self.C_i, 0, alpha, gamma, R),
-                            h.nnz, self.n_owned * w, h.x_rows)
-                return
-            self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i, self.C_i, 0),
+            step = affine or AffineStep()
+            norm = (self.X_i, norm_acc) if norm_acc is not None else None
+            self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_i, self.C_i,
+                                             0, step.alpha, step.gamma, step.R,
+                                             norm=norm),
                         h.nnz, self.n_owned * w, h.x_rows)
             return
 
@@ -821,8 +830,7 @@ class ArrowSlimMPI(ArrowMatrix):
         # hub gathers are fabric-bound while the banded rest launch is not,
         # so co-running them fills the slack. Fork-join via
         # events (capture-legal for hipGraph).
-        import os as _os
-        par = (_os.environ.get('ARROW_PAR_ROW0', '0') == '1'
+        par = (os.environ.get('ARROW_PAR_ROW0', '0') == '1'
                and bool(self._A_row0))
         stream_ctx = None
         if par:
@@ -905,10 +913,9 @@ class ArrowSlimMPI(ArrowMatrix):
             # join: the main stream's C_0 consumers (head copy / X_0 swap)
             # wait for the side-stream row-0 work
             torch.cuda.current_stream().wait_event(ev_r)
-        import os as _os2
         defer = (self.allreduce_x0 and self.comm.size > 1
                  and not self.banded
-                 and _os2.environ.get('ARROW_X0_DEFER', '1') != '0')
+                 and os.environ.get('ARROW_X0_DEFER', '1') != '0')
         if defer:
             self._pending_x0_works = [wk for wk in reduce_works
                                       if wk is not None]

@@ -32,6 +32,12 @@ class CpuBackend:
                 "is the scipy parity reference, which has no bfloat16")
         self.np_dtype = np.dtype(dtype)
         self.torch_dtype = _TORCH_DTYPE[self.np_dtype]
+        # the feature side of the surface, as on GpuBackend
+        self.bf16 = False
+        self.feat_dtype = self.np_dtype
+        self.feat_itemsize = self.np_dtype.itemsize
+        self.norm_launches = 0      # no scipy launch measures its own step
+        self.diffnorm_launches = 0
 
     def zeros(self, shape):
         return torch.zeros(shape, dtype=self.torch_dtype)
@@ -91,6 +97,7 @@ class CpuBackend:
         """acc[0] += sum (C - D)^2, acc[1] += sum C^2, the definition of the
         step norms in float64 (D None means 0); the parity reference of the
         GPU kernels."""
+        self.diffnorm_launches += 1
         c = C.numpy().astype(np.float64)
         d = D.numpy().astype(np.float64) if D is not None else 0.0
         acc[0] += float(np.square(c - d).sum())
@@ -156,42 +163,33 @@ class GpuBackend:
         return hip.CsrBlockGPU(csr, dtype=self.np_dtype)
 
     @staticmethod
-    def _affine_kw(alpha, gamma, R, C):
-        """Keywords for the affine entry points, none for the plain step."""
-        if alpha == 1.0 and gamma == 0.0 and R is None:
-            return {}
-        if R is not None:
-            assert R.is_contiguous() and R.shape == C.shape \
-                and R.dtype == C.dtype
-        return dict(alpha=alpha, gamma=gamma,
-                    R_ptr=R.data_ptr() if R is not None else 0)
+    def _ptr_like(C, T) -> int:
+        """data_ptr() of a tensor laid out like C (R or D); 0 for None."""
+        if T is None:
+            return 0
+        assert T.is_contiguous() and T.shape == C.shape and T.dtype == C.dtype
+        return T.data_ptr()
 
-    @staticmethod
-    def _norm_kw(norm, C):
-        """norm=(D, acc) as the pointer pair hip.py takes (D None: D = 0)."""
-        if norm is None:
-            return {}
-        D, acc = norm
-        assert D is None or (D.is_contiguous() and D.shape == C.shape
-                             and D.dtype == C.dtype)
-        assert acc.dtype == torch.float64 and acc.numel() == 2 \
-            and acc.device == C.device
-        return dict(norm=(D.data_ptr() if D is not None else 0,
-                          acc.data_ptr()))
+    def _launch(self, spmm, xs, C, beta, alpha, gamma, R, norm):
+        """block.spmm (one X in xs) or block.spmm_dual (two) on tensors.
+        hip.py picks the entry point: the plain one when alpha, gamma, R and
+        norm are all at their defaults."""
+        assert all(X.is_contiguous() for X in xs) and C.is_contiguous()
+        if norm is not None:
+            D, acc = norm
+            assert acc.dtype == torch.float64 and acc.numel() == 2 \
+                and acc.device == C.device
+            self.norm_launches += 1
+            norm = (self._ptr_like(C, D), acc.data_ptr())
+        spmm(*(X.data_ptr() for X in xs), C.data_ptr(), C.shape[1], beta,
+             self._stream(), feat_dtype=self.feat_dtype, alpha=alpha,
+             gamma=gamma, R_ptr=self._ptr_like(C, R), norm=norm)
 
     def spmm_block(self, block: hip.CsrBlockGPU, X: torch.Tensor, C: torch.Tensor, beta: int,
                    alpha: float = 1.0, gamma: float = 0.0, R=None, norm=None):
         """norm=(D, acc): the launch also adds sum (C - D)^2 and sum C^2 into
         the two float64 of the device tensor acc (beta 0 only)."""
-        assert X.is_contiguous() and C.is_contiguous()
-        kw = self._affine_kw(alpha, gamma, R, C)
-        if norm is not None:
-            self.norm_launches += 1
-            kw = dict(alpha=alpha, gamma=gamma,
-                      R_ptr=R.data_ptr() if R is not None else 0,
-                      **self._norm_kw(norm, C))
-        block.spmm(X.data_ptr(), C.data_ptr(), C.shape[1], beta, self._stream(),
-                   feat_dtype=self.feat_dtype, **kw)
+        self._launch(block.spmm, (X,), C, beta, alpha, gamma, R, norm)
 
     def upload_arrays(self, shape, indptr, indices, data, row_ids=None,
                       col_items=False) -> hip.CsrBlockGPU:
@@ -202,26 +200,20 @@ class GpuBackend:
     def spmm_dual(self, block: hip.CsrBlockGPU, X0: torch.Tensor,
                   X1: torch.Tensor, C: torch.Tensor, beta: int,
                   alpha: float = 1.0, gamma: float = 0.0, R=None, norm=None):
-        assert X0.is_contiguous() and X1.is_contiguous() and C.is_contiguous()
-        kw = self._affine_kw(alpha, gamma, R, C)
-        if norm is not None:
-            self.norm_launches += 1
-            kw = dict(alpha=alpha, gamma=gamma,
-                      R_ptr=R.data_ptr() if R is not None else 0,
-                      **self._norm_kw(norm, C))
-        block.spmm_dual(X0.data_ptr(), X1.data_ptr(), C.data_ptr(),
-                        C.shape[1], beta, self._stream(),
-                        feat_dtype=self.feat_dtype, **kw)
+        self._launch(block.spmm_dual, (X0, X1), C, beta, alpha, gamma, R,
+                     norm)
 
     def diffnorm_rows(self, C: torch.Tensor, D, acc: torch.Tensor):
         """acc[0] += sum (C - D)^2, acc[1] += sum C^2 over the rows of C
         (arrow_diffnorm_rows_*; D None means 0)."""
-        assert C.is_contiguous()
+        assert C.is_contiguous() and acc.dtype == torch.float64 \
+            and acc.numel() == 2 and acc.device == C.device
+        D_ptr = self._ptr_like(C, D)
         self.diffnorm_launches += 1
         if C.shape[0]:
-            hip.diffnorm_rows(C.data_ptr(), self._norm_kw((D, acc), C)['norm'][0],
-                              C.shape[0], C.shape[1], acc.data_ptr(),
-                              self._stream(), dtype=self.feat_dtype)
+            hip.diffnorm_rows(C.data_ptr(), D_ptr, C.shape[0], C.shape[1],
+                              acc.data_ptr(), self._stream(),
+                              dtype=self.feat_dtype)
 
     def norm_acc(self) -> torch.Tensor:
         """The two-double device accumulator of the step norms."""
@@ -229,12 +221,11 @@ class GpuBackend:
 
     def axpby_rows(self, C: torch.Tensor, R, alpha: float, gamma: float):
         """C = alpha * C + gamma * R in place (arrow_axpby_rows_*)."""
-        assert C.is_contiguous() and (R is None or (
-            R.is_contiguous() and R.shape == C.shape and R.dtype == C.dtype))
+        assert C.is_contiguous()
+        R_ptr = self._ptr_like(C, R)
         if C.shape[0]:
-            hip.axpby_rows(C.data_ptr(), R.data_ptr() if R is not None else 0,
-                           C.shape[0], C.shape[1], alpha, gamma,
-                           self._stream(), dtype=self.feat_dtype)
+            hip.axpby_rows(C.data_ptr(), R_ptr, C.shape[0], C.shape[1], alpha,
+                           gamma, self._stream(), dtype=self.feat_dtype)
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         out = torch.empty((idx.shape[0], src.shape[1]), dtype=self.torch_dtype,

@@ -61,102 +61,47 @@ def _load():
     lib.arrow_csr_set_queue.restype = ctypes.c_int
     lib.arrow_csr_set_qblocks.argtypes = [ctypes.c_int64, ctypes.c_int]
     lib.arrow_csr_set_qblocks.restype = ctypes.c_int
-    lib.arrow_spmm.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                               ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.arrow_spmm.restype = ctypes.c_int
-    lib.arrow_spmm_dual.argtypes = [ctypes.c_int64, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
-    lib.arrow_spmm_dual.restype = ctypes.c_int
-    lib.arrow_spmm_plan.argtypes = [ctypes.c_int64, ctypes.c_int64,
-                                    ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
-                                    ctypes.c_int]
-    lib.arrow_spmm_plan.restype = ctypes.c_int
-    for name in ('arrow_gather_rows_f32', 'arrow_scatter_rows_f32',
-                 'arrow_scatter_add_rows_f32'):
+    # Everything below is written once for all precisions:
+    #   ABI 1003  float64: arrow_csr_create_f64 / arrow_csr_dtype, the _f64
+    #             SpMM, plan and routing entry points
+    #   ABI 1004  bfloat16 features: the _bf16 entry points; no create call,
+    #             they take a float32 structure handle
+    #   ABI 1005  affine step: arrow_spmm[_dual]_affine*, arrow_axpby_rows_*
+    #   ABI 1006  step norms: arrow_spmm[_dual]_affine_norm*,
+    #             arrow_diffnorm_rows_*
+    i64, cint, ptr, dbl = (ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                          ctypes.c_double)
+
+    def declare(name, argtypes, restype=ctypes.c_int):
         fn = getattr(lib, name)
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    for name in ('arrow_permute_rows_f32', 'arrow_permute_add_rows_f32'):
-        fn = getattr(lib, name)
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
-                       ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    # float64 entry points (ABI 1003)
-    lib.arrow_csr_create_f64.restype = ctypes.c_int64
-    lib.arrow_csr_create_f64.argtypes = [
-        ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
-        ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int32),
-        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64),
-        ctypes.c_int]
-    lib.arrow_csr_dtype.argtypes = [ctypes.c_int64]
-    lib.arrow_csr_dtype.restype = ctypes.c_int
-    lib.arrow_spmm_f64.argtypes = lib.arrow_spmm.argtypes
-    lib.arrow_spmm_f64.restype = ctypes.c_int
-    lib.arrow_spmm_dual_f64.argtypes = lib.arrow_spmm_dual.argtypes
-    lib.arrow_spmm_dual_f64.restype = ctypes.c_int
-    lib.arrow_spmm_plan_f64.argtypes = lib.arrow_spmm_plan.argtypes
-    lib.arrow_spmm_plan_f64.restype = ctypes.c_int
-    for name in ('arrow_gather_rows', 'arrow_scatter_rows',
-                 'arrow_scatter_add_rows', 'arrow_permute_rows',
-                 'arrow_permute_add_rows'):
-        fn = getattr(lib, name + '_f64')
-        fn.argtypes = getattr(lib, name + '_f32').argtypes
-        fn.restype = ctypes.c_int
-    # bfloat16-feature entry points (ABI 1004); no create call, they take a
-    # float32 structure handle
-    for name in ('arrow_spmm', 'arrow_spmm_dual', 'arrow_spmm_plan'):
-        fn = getattr(lib, name + '_bf16')
-        fn.argtypes = getattr(lib, name).argtypes
-        fn.restype = ctypes.c_int
-    for name in ('arrow_gather_rows', 'arrow_scatter_rows',
-                 'arrow_scatter_add_rows', 'arrow_permute_rows',
-                 'arrow_permute_add_rows'):
-        fn = getattr(lib, name + '_bf16')
-        fn.argtypes = getattr(lib, name + '_f32').argtypes
-        fn.restype = ctypes.c_int
-    # affine step (ABI 1005): (handle, X0[, X1], C, R, k, alpha, gamma, beta,
-    # stream) and the stand-alone tail (C, R, n, k, alpha, gamma, stream)
-    for sfx in ('', '_f64', '_bf16'):
-        fn = getattr(lib, 'arrow_spmm_affine' + sfx)
-        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
-                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-        fn = getattr(lib, 'arrow_spmm_dual_affine' + sfx)
-        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                       ctypes.c_double, ctypes.c_double, ctypes.c_int,
-                       ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    for sfx in ('_f32', '_f64', '_bf16'):
-        fn = getattr(lib, 'arrow_axpby_rows' + sfx)
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                       ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                       ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    # step norms (ABI 1006): the affine lists with (D, acc) after R, and the
-    # stand-alone pass (C, D, n, k, acc, stream)
-    for sfx in ('', '_f64', '_bf16'):
-        fn = getattr(lib, 'arrow_spmm_affine_norm' + sfx)
-        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_int64, ctypes.c_double, ctypes.c_double,
-                       ctypes.c_int, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-        fn = getattr(lib, 'arrow_spmm_dual_affine_norm' + sfx)
-        fn.argtypes = [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                       ctypes.c_void_p, ctypes.c_int64, ctypes.c_double,
-                       ctypes.c_double, ctypes.c_int, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
-    for sfx in ('_f32', '_f64', '_bf16'):
-        fn = getattr(lib, 'arrow_diffnorm_rows' + sfx)
-        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                       ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]
-        fn.restype = ctypes.c_int
+        fn.argtypes, fn.restype = argtypes, restype
+    declare('arrow_csr_create_f64', [
+        i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32),
+        ctypes.POINTER(dbl), ctypes.POINTER(i64), cint], restype=i64)
+    declare('arrow_csr_dtype', [i64])
+    for sfx in _SPMM_SUFFIX.values():
+        for dual in (False, True):
+            for tier in _SPMM_TIERS:
+                # the list the call itself passes, with types for values
+                declare(_spmm_symbol(dual, tier, sfx), _spmm_args(
+                    tier, i64, [ptr] * (2 if dual else 1), ptr, ptr, ptr, ptr,
+                    i64, dbl, dbl, cint, ptr))
+        declare('arrow_spmm_plan' + sfx,
+                [i64, i64, cint, ctypes.POINTER(ctypes.c_int32), cint])
+    for sfx in _SPMM_SUFFIX:
+        for argtypes, names in (
+                # (a, b, idx, n, k, stream)
+                ([ptr, ptr, ptr, i64, i64, ptr],
+                 ('gather_rows', 'scatter_rows', 'scatter_add_rows')),
+                # (dst, src, dst_idx, src_idx, n, k, stream)
+                ([ptr, ptr, ptr, ptr, i64, i64, ptr],
+                 ('permute_rows', 'permute_add_rows')),
+                # the stand-alone tail (C, R, n, k, alpha, gamma, stream)
+                ([ptr, ptr, i64, i64, dbl, dbl, ptr], ('axpby_rows',)),
+                # the stand-alone norms (C, D, n, k, acc, stream)
+                ([ptr, ptr, i64, i64, ptr, ptr], ('diffnorm_rows',))):
+            for name in names:
+                declare(f'arrow_{name}_{sfx}', argtypes)
     _lib = lib
     return lib
 
@@ -197,6 +142,32 @@ def _suffix(dtype) -> str:
         return 'f64'
     raise TypeError(f"the HIP kernels compute in float32 or float64, "
                     f"not {dtype!r}")
+
+
+# the SpMM family (arrow_spmm*, arrow_spmm_plan*) spells float32 with no
+# suffix; every other entry point takes '_' + _suffix(dtype)
+_SPMM_SUFFIX = {'f32': '', 'f64': '_f64', 'bf16': '_bf16'}
+_SPMM_TIERS = ('', '_affine', '_affine_norm')
+
+
+def _spmm_symbol(dual: bool, tier: str, sfx: str) -> str:
+    return 'arrow_spmm' + ('_dual' if dual else '') + tier + sfx
+
+
+def _spmm_args(tier, handle, xs, C, R, D, acc, k, alpha, gamma, beta, stream):
+    """The positional list of arrow_spmm[_dual]<tier>* (include/arrow_spmm.h):
+    handle, X.., C, [R], [D, acc], k, [alpha, gamma], beta, stream. Called
+    with values to launch and with ctypes types to declare, so a declaration
+    cannot drift from its call."""
+    args = [handle, *xs, C]
+    if tier:
+        args.append(R)
+    if tier == '_affine_norm':
+        args += [D, acc]
+    args.append(k)
+    if tier:
+        args += [alpha, gamma]
+    return args + [beta, stream]
 
 
 class CsrBlockGPU:
@@ -253,13 +224,23 @@ class CsrBlockGPU:
     def _entry(self, name: str, feat_dtype):
         """The SpMM entry point for features of feat_dtype (None: the
         structure's own precision)."""
-        sfx = {'f32': '', 'f64': '_f64', 'bf16': '_bf16'}[
+        sfx = _SPMM_SUFFIX[
             _suffix(self.dtype if feat_dtype is None else feat_dtype)]
         return getattr(_load(), name + sfx), name + sfx
 
-    @staticmethod
-    def _is_affine(alpha, gamma, R_ptr) -> bool:
-        return alpha != 1.0 or gamma != 0.0 or bool(R_ptr)
+    def _spmm(self, xs, C_ptr, k, beta, stream, feat_dtype, alpha, gamma,
+              R_ptr, norm):
+        """spmm (one X pointer in xs) and spmm_dual (two): the norm tier when
+        norm is given, else the affine tier when alpha, gamma or R_ptr is,
+        else the plain entry point."""
+        tier = ('_affine_norm' if norm is not None else
+                '_affine' if alpha != 1.0 or gamma != 0.0 or R_ptr else '')
+        fn, name = self._entry(_spmm_symbol(len(xs) == 2, tier, ''),
+                               feat_dtype)
+        D_ptr, acc_ptr = norm if norm is not None else (0, 0)
+        _check(fn(*_spmm_args(tier, self._handle, xs, C_ptr, R_ptr or None,
+                              D_ptr or None, acc_ptr or None, k, float(alpha),
+                              float(gamma), beta, stream)), name)
 
     def spmm(self, X_ptr: int, C_ptr: int, k: int, beta: int, stream: int = 0,
              feat_dtype=None, alpha: float = 1.0, gamma: float = 0.0,
@@ -271,19 +252,8 @@ class CsrBlockGPU:
         called, as before. norm=(D_ptr, acc_ptr): the step also adds
         sum (C - D)^2 and sum C^2 into the two device doubles at acc_ptr
         (arrow_spmm_affine_norm*; beta 0 only, D_ptr 0 means D = 0)."""
-        if norm is not None:
-            fn, name = self._entry('arrow_spmm_affine_norm', feat_dtype)
-            _check(fn(self._handle, X_ptr, C_ptr, R_ptr or None,
-                      norm[0] or None, norm[1] or None, k, float(alpha),
-                      float(gamma), beta, stream), name)
-            return
-        if self._is_affine(alpha, gamma, R_ptr):
-            fn, name = self._entry('arrow_spmm_affine', feat_dtype)
-            _check(fn(self._handle, X_ptr, C_ptr, R_ptr or None, k,
-                      float(alpha), float(gamma), beta, stream), name)
-            return
-        fn, name = self._entry('arrow_spmm', feat_dtype)
-        _check(fn(self._handle, X_ptr, C_ptr, k, beta, stream), name)
+        self._spmm((X_ptr,), C_ptr, k, beta, stream, feat_dtype, alpha, gamma,
+                   R_ptr, norm)
 
     def set_xcd_remap(self, enable: bool):
         _check(_load().arrow_csr_set_xcd_remap(self._handle, 1 if enable else 0),
@@ -307,19 +277,8 @@ class CsrBlockGPU:
         upload as -(idx+1)) read X1 (see include/arrow_spmm.h). alpha, gamma,
         R_ptr and norm as in spmm (arrow_spmm_dual_affine*,
         arrow_spmm_dual_affine_norm*)."""
-        if norm is not None:
-            fn, name = self._entry('arrow_spmm_dual_affine_norm', feat_dtype)
-            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, R_ptr or None,
-                      norm[0] or None, norm[1] or None, k, float(alpha),
-                      float(gamma), beta, stream), name)
-            return
-        if self._is_affine(alpha, gamma, R_ptr):
-            fn, name = self._entry('arrow_spmm_dual_affine', feat_dtype)
-            _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, R_ptr or None, k,
-                      float(alpha), float(gamma), beta, stream), name)
-            return
-        fn, name = self._entry('arrow_spmm_dual', feat_dtype)
-        _check(fn(self._handle, X0_ptr, X1_ptr, C_ptr, k, beta, stream), name)
+        self._spmm((X0_ptr, X1_ptr), C_ptr, k, beta, stream, feat_dtype, alpha,
+                   gamma, R_ptr, norm)
 
     def __del__(self):
         if getattr(self, '_handle', None) is not None and _lib is not None:
@@ -402,8 +361,7 @@ def spmm_plan(k: int, nnz: int, queue_mode: int = -1,
     of `nnz` nonzeros at width k (arrow_spmm_plan / _f64 / _bf16; needs no
     device). The ARROW_* kernel-tuning variables are read once per process,
     on first use."""
-    name = {'f32': 'arrow_spmm_plan', 'f64': 'arrow_spmm_plan_f64',
-            'bf16': 'arrow_spmm_plan_bf16'}[_suffix(dtype)]
+    name = 'arrow_spmm_plan' + _SPMM_SUFFIX[_suffix(dtype)]
     out = (ctypes.c_int32 * len(PLAN_FIELDS))()
     n = _check(getattr(_load(), name)(int(k), int(nnz), int(queue_mode), out,
                                       len(PLAN_FIELDS)), name)

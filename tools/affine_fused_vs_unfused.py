@@ -101,7 +101,7 @@ def main():
     assert calls[0] == 0, "the fused layout called the tail kernel"
     eng.backend.axpby_rows = inner
     Rbuf = eng._R
-    arrow._affine = eng._affine = None      # plain launches, R kept resident
+    arrow.clear_affine_step()   # plain launches; Rbuf keeps R resident
 
     def unfused():
         arrow.step()
