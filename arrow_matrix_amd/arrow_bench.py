@@ -32,7 +32,9 @@ def bench_spmm(path: Union[str, None],
                slim: bool = True,
                npy_format: bool = True,
                damping: float = None,
-               tol: float = None):
+               tol: float = None,
+               normalize: str = None,
+               normalize_abs: bool = False):
     """damping=D (not in the reference; default off, nothing changes without
     it) iterates the damped step X <- D * A@X + (1 - D) * X0 instead of
     drawing fresh features every iteration: X0, the first iteration's
@@ -40,7 +42,10 @@ def bench_spmm(path: Union[str, None],
     shape). Single process only. tol=T (needs damping) tracks the step norms
     and stops after the first iteration with ||X_new - X_old|| / ||X_new||
     <= T, printing the steps taken and the last ratio; without it nothing
-    changes."""
+    changes. normalize='row' | 'col' | 'sym' (default off) normalises the
+    resident matrix on the device after the load and before the first step
+    (ArrowDecompositionMPI.normalize_operator; normalize_abs sums |a_ij|):
+    'col' is PageRank's column-stochastic operator. Single process only."""
     if tol is not None and damping is None:
         raise ValueError("bench_spmm: tol needs damping (a plain run draws "
                          "fresh features every iteration)")
@@ -91,6 +96,10 @@ def bench_spmm(path: Union[str, None],
     arrow.zero_rhs(width, n_features, dtype=datatype)
     comm.barrier()
     wb_logging.log({"init_time": time.perf_counter() - tic})
+    if normalize is not None:
+        tic = time.perf_counter()
+        arrow.normalize_operator(normalize, absolute=normalize_abs)
+        wb_logging.log({"normalize_time": time.perf_counter() - tic})
 
     eng0 = arrow.engines[0]
     if tol is not None:

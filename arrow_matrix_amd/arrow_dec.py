@@ -33,7 +33,7 @@ import torch
 
 from . import graphio, hip, tables
 from .arrow_matrix import ArrowMatrix
-from .arrow_slim import AffineStep, ArrowSlimMPI
+from .arrow_slim import AffineStep, ArrowSlimMPI, normalizing_factors
 from .comm import Comm, default_comm
 from .common import wb_logging
 
@@ -470,6 +470,106 @@ class ArrowDecompositionMPI:
                 if tol is not None and rel <= tol:
                     return t, rel
         return max_steps, rel
+
+    # -- operator scaling ----------------------------------------------------
+
+    def _operator_parts(self):
+        """The recomposed matrix as its resident pieces beyond part 0, each
+        (i, piece, rows_folded, cols_folded): piece is part i's engine, or
+        its folded structure; rows_folded / cols_folded say that the piece's
+        rows / columns are already in part 0's layout (else in part i's,
+        reached through _fold_maps[i] = (M_i, R_i))."""
+        for i in range(1, self.decomposition_length):
+            if self._folded is None:
+                yield i, self.engines[i], False, False
+            else:
+                yield i, self._folded[i - 1], True, self._fold_cols
+
+    def _check_operator_scaling(self, who: str) -> int:
+        if self.comm.size > 1:
+            raise NotImplementedError(
+                f"{who} is single-process only (no multi-GPU rig to validate "
+                f"the reduced sums and the broadcast factors against)")
+        return int(self.n_blocks[0]) * self.width
+
+    @staticmethod
+    def _gather_factors(v, index):
+        """v[index] with the factor 0 where index is -1 (rows the cascade
+        discards, feature rows no part-0 row feeds); None stays None."""
+        if v is None:
+            return None
+        return np.where(index >= 0, v[np.clip(index, 0, None)], 0.0)
+
+    def operator_sums(self, absolute: bool = False):
+        """(row_sums, col_sums) of the RECOMPOSED matrix: float64 numpy
+        vectors of n_blocks[0] * width entries in part 0's layout, exactly
+        as features and the residual are. Every resident structure is summed
+        on the device (arrow_csr_sums); the per-part vectors are routed into
+        part 0's layout on the host, once (DESIGN.md §operator scaling).
+        Single process only."""
+        n0 = self._check_operator_scaling('operator_sums')
+        eng0 = self.engines[0]
+        be = eng0.backend
+        absolute = bool(absolute)
+        rows, cols = eng0._operator_sums_stripe(absolute)
+        for i, piece, rows_folded, cols_folded in self._operator_parts():
+            M_i, R_i = self._fold_maps[i]
+            if isinstance(piece, ArrowSlimMPI):
+                ri, ci = piece._operator_sums_stripe(absolute)
+            else:
+                ni = int(self.n_blocks[i]) * self.width
+                rv = be.scale_vector(np.zeros(n0))
+                cv = be.scale_vector(np.zeros(n0 if cols_folded else ni))
+                be.block_sums(piece, rv, cv, None, absolute)
+                be.synchronize()
+                ri, ci = rv.cpu().numpy(), cv.cpu().numpy()
+            if rows_folded:
+                rows += ri
+            else:
+                np.add.at(rows, R_i[R_i >= 0], ri[R_i >= 0])
+            if cols_folded:
+                cols += ci
+            else:
+                np.add.at(cols, M_i[M_i >= 0], ci[M_i >= 0])
+        return rows, cols
+
+    def scale_operator(self, row_scale=None, col_scale=None) -> None:
+        """A <- diag(row_scale) A diag(col_scale) on the recomposed matrix,
+        in place on the resident values of every part (arrow_csr_scale; one
+        rounding per value). Vectors in part 0's layout, None is no factor:
+        part i takes row_scale[R_i] and col_scale[M_i] through the fold maps.
+        Needs no zero_rhs; feature buffers, the affine step and a captured
+        graph stay valid. Single process only."""
+        n0 = self._check_operator_scaling('scale_operator')
+        eng0 = self.engines[0]
+        be = eng0.backend
+        r = eng0._stripe_vector('scale_operator', 'row_scale', row_scale, n0)
+        c = eng0._stripe_vector('scale_operator', 'col_scale', col_scale, n0)
+        if r is None and c is None:
+            return
+        eng0._operator_scale_stripe(r, c)
+        for i, piece, rows_folded, cols_folded in self._operator_parts():
+            M_i, R_i = self._fold_maps[i]
+            ri = r if rows_folded else self._gather_factors(r, R_i)
+            ci = c if cols_folded else self._gather_factors(c, M_i)
+            if isinstance(piece, ArrowSlimMPI):
+                piece._operator_scale_stripe(ri, ci)
+            else:
+                be.block_scale(piece,
+                               None if ri is None else be.scale_vector(ri),
+                               None if ci is None else be.scale_vector(ci),
+                               None)
+                be.synchronize()
+
+    def normalize_operator(self, kind: str, absolute: bool = False):
+        """Normalise the recomposed matrix ('row': D^-1 A, 'col': A D^-1,
+        'sym': D_r^-1/2 A D_c^-1/2; see ArrowSlimMPI.normalize_operator) and
+        return the (row_scale, col_scale) applied, in part 0's layout.
+        operator_sums followed by scale_operator, nothing else."""
+        row_sums, col_sums = self.operator_sums(absolute)
+        r, c = normalizing_factors(kind, row_sums, col_sums)
+        self.scale_operator(r, c)
+        return r, c
 
     # -- iteration -----------------------------------------------------------
 

@@ -44,6 +44,35 @@ class AffineStep(NamedTuple):
     R: Optional[torch.Tensor] = None
 
 
+def normalizing_factors(kind: str, row_sums, col_sums):
+    """(row_scale, col_scale) of normalize_operator from the sums: 'row'
+    (1/rowsum, None), 'col' (None, 1/colsum), 'sym' (1/sqrt(rowsum),
+    1/sqrt(colsum)). A zero sum (padding rows, isolated vertices) gives the
+    factor 0."""
+    def inverse(s, power):
+        s = np.asarray(s, dtype=np.float64)
+        out = np.zeros_like(s)
+        nz = s != 0
+        out[nz] = 1.0 / (s[nz] if power == 1 else np.sqrt(s[nz]))
+        return out
+    if kind == 'row':
+        return inverse(row_sums, 1), None
+    if kind == 'col':
+        return None, inverse(col_sums, 1)
+    if kind == 'sym':
+        for name, s in (('row', row_sums), ('column', col_sums)):
+            neg = np.flatnonzero(np.asarray(s) < 0)
+            if neg.size:
+                raise ValueError(
+                    f"normalize_operator('sym'): {name} {int(neg[0])} has the "
+                    f"negative sum {float(s[neg[0]])!r}, which has no square "
+                    f"root; pass absolute=True to normalise by the sums of "
+                    f"|a_ij|")
+        return inverse(row_sums, 2), inverse(col_sums, 2)
+    raise ValueError(f"normalize_operator: kind must be 'row', 'col' or "
+                     f"'sym', not {kind!r}")
+
+
 class ArrowSlimMPI(ArrowMatrix):
 
     def __init__(self, comm: Optional[Comm] = None, tiles_per_side: Optional[int] = None,
@@ -641,6 +670,127 @@ class ArrowSlimMPI(ArrowMatrix):
         """The stand-alone pass: the layouts whose result no single launch
         finishes (and the cpu device)."""
         self.backend.diffnorm_rows(self.C_i, self.X_i, norm_acc)
+
+    # -- operator scaling ------------------------------------------------------
+
+    def _check_operator_scaling(self, who: str) -> int:
+        """Single process only; returns the length of the stripe vectors."""
+        if self.comm.size > 1:
+            raise NotImplementedError(
+                f"{who} is single-process only: at world>1 the sums of block "
+                f"row 0 and of every column would have to be reduced across "
+                f"ranks and the factors broadcast, and there is no multi-GPU "
+                f"rig to validate that")
+        if self.width is None:
+            raise ValueError(f"{who}: load the matrix first")
+        return self.n_owned * self.width
+
+    def _operator_structures(self):
+        """Every resident structure of this engine (single process) as
+        (block, row_offset, x1_is_head, cols): block writes the stripe rows
+        from row_offset on; its columns c >= 0 read stripe row c (cols None,
+        the merged GPU structures) or stripe row cols[c] (the cpu device's
+        per-block scipy matrices, column-compacted or not); x1_is_head says
+        that a negative column -c-1 reads X_0 = the stripe head, row c."""
+        w = self.width
+        if self.backend.device == 'cuda':
+            if self._A_all is not None:
+                yield self._A_all, 0, True, None
+            for h, lo, _ in (self._A_row0 or []):
+                yield h, lo, True, None
+            for h, lo, _ in (self._A_rest or []):
+                yield h, self._rest_row_offset + lo, True, None
+            if self._A_col is not None:
+                yield self._A_col, self._rest_row_offset, True, None
+            return
+        for j in range(self.n_owned):
+            lo = self.A_lo[j] if self.A_lo else None
+            hi = self.A_hi[j] if self.A_hi else None
+            for slot, blk, row_off, col_off in (
+                    (0, self.A_0i[j], 0, j * w), (1, self.A_ii[j], j * w, j * w),
+                    (2, self.A_i0[j], j * w, 0), (None, lo, j * w, (j - 1) * w),
+                    (None, hi, j * w, (j + 1) * w)):
+                if blk is None:
+                    continue
+                kept = None if slot is None else self._nnz_columns[j][slot]
+                cols = col_off + (np.arange(w) if kept is None else kept)
+                yield blk, row_off, True, cols
+
+    def _operator_sums_stripe(self, absolute: bool):
+        """(row sums, column sums) of this engine's matrix as float64 numpy
+        vectors in the stripe layout."""
+        be = self.backend
+        n = self.n_owned * self.width
+        row, col = be.scale_vector(np.zeros(n)), be.scale_vector(np.zeros(n))
+        for blk, off, x1_is_head, cols in self._operator_structures():
+            assert x1_is_head
+            if cols is None:
+                be.block_sums(blk, row[off:], col, col, absolute)
+            else:
+                part = be.scale_vector(np.zeros(blk.shape[1]))
+                be.block_sums(blk, row[off:], part, None, absolute)
+                col.numpy()[cols] += part.numpy()   # cpu device only
+        be.synchronize()
+        return row.cpu().numpy(), col.cpu().numpy()
+
+    def _operator_scale_stripe(self, r, c) -> None:
+        """A <- diag(r) A diag(c) on every resident structure; r and c are
+        float64 numpy vectors in the stripe layout, or None for no factor."""
+        if r is None and c is None:
+            return
+        be = self.backend
+        r = None if r is None else be.scale_vector(r)
+        c = None if c is None else be.scale_vector(c)
+        for blk, off, x1_is_head, cols in self._operator_structures():
+            assert x1_is_head
+            rv = None if r is None else r[off:]
+            if cols is None:
+                be.block_scale(blk, rv, c, c)
+            else:
+                be.block_scale(blk, rv, None if c is None
+                               else c[torch.from_numpy(cols)], None)
+        # the vectors die with this call: the passes must have read them
+        be.synchronize()
+
+    def _stripe_vector(self, who, name, v, n):
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=np.float64)
+        if v.shape != (n,):
+            raise ValueError(f"{who}: {name} has shape {v.shape}, the matrix "
+                             f"has {n} rows and columns")
+        return v
+
+    def operator_sums(self, absolute: bool = False):
+        """(row_sums, col_sums) of the resident matrix: float64 numpy vectors
+        of n_blocks * width entries in this engine's layout (as features
+        are). absolute sums |a_ij|. Summed on the device, in double
+        (arrow_csr_sums; DESIGN.md §operator scaling). Single process only."""
+        self._check_operator_scaling('operator_sums')
+        return self._operator_sums_stripe(bool(absolute))
+
+    def scale_operator(self, row_scale=None, col_scale=None) -> None:
+        """A <- diag(row_scale) A diag(col_scale) in place on the resident
+        values, each rounded once: val = T((float64(val) * r) * c)
+        (arrow_csr_scale). Vectors as operator_sums returns them; None is no
+        factor. Needs no zero_rhs; feature buffers, an affine step and a
+        captured graph stay valid (no pointer changes). Single process only."""
+        n = self._check_operator_scaling('scale_operator')
+        self._operator_scale_stripe(
+            self._stripe_vector('scale_operator', 'row_scale', row_scale, n),
+            self._stripe_vector('scale_operator', 'col_scale', col_scale, n))
+
+    def normalize_operator(self, kind: str, absolute: bool = False):
+        """Normalise the resident matrix and return the (row_scale, col_scale)
+        applied (None for the side left alone): 'row' divides every row by
+        its sum (D^-1 A, random-walk diffusion), 'col' every column (A D^-1,
+        PageRank), 'sym' scales by 1/sqrt of both (D_r^-1/2 A D_c^-1/2, GCN /
+        APPNP). A zero sum gives the factor 0. operator_sums followed by
+        scale_operator, nothing else."""
+        row_sums, col_sums = self.operator_sums(absolute)
+        r, c = normalizing_factors(kind, row_sums, col_sums)
+        self.scale_operator(r, c)
+        return r, c
 
     def _select_result_buffer(self):
         if self.X_i is None or self.C_i.data_ptr() != self.X_i.data_ptr():

@@ -107,6 +107,58 @@ class CpuBackend:
         """The two-double accumulator of the step norms."""
         return torch.zeros(2, dtype=torch.float64)
 
+    # -- operator scaling (the parity reference of arrow_csr_sums / _scale) --
+
+    def scale_vector(self, x) -> torch.Tensor:
+        """A float64 vector of the operator passes, on this backend."""
+        return torch.from_numpy(np.array(x, dtype=np.float64))
+
+    @staticmethod
+    def _block_coo(block):
+        """(csr, output row per nonzero) of a scipy block or of a folded
+        (csr, row_ids) pair."""
+        csr, rid = block if isinstance(block, tuple) else (block, None)
+        rows = np.repeat(np.arange(csr.shape[0], dtype=np.int64),
+                         np.diff(csr.indptr))
+        return csr, (rows if rid is None else np.asarray(rid)[rows])
+
+    def block_sums(self, block, row_sum, col_sum0, col_sum1, absolute=False):
+        """ADD the sums of block's stored values into the float64 vectors,
+        indexed as arrow_csr_sums indexes them: row_sum by output row (after
+        the row_ids of a folded pair), col_sum0 by column c >= 0, col_sum1
+        at -c-1 for c < 0. None skips an output."""
+        if row_sum is None and col_sum0 is None and col_sum1 is None:
+            raise ValueError("block_sums: all three outputs are None")
+        csr, rows = self._block_coo(block)
+        v = csr.data.astype(np.float64)
+        if absolute:
+            v = np.abs(v)
+        cols = csr.indices.astype(np.int64)
+        pos = cols >= 0
+        if row_sum is not None:
+            np.add.at(row_sum.numpy(), rows, v)
+        if col_sum0 is not None:
+            np.add.at(col_sum0.numpy(), cols[pos], v[pos])
+        if col_sum1 is not None:
+            np.add.at(col_sum1.numpy(), -cols[~pos] - 1, v[~pos])
+
+    def block_scale(self, block, r, c0, c1):
+        """val = T((float64(val) * r) * c) in place, the rounding formula of
+        arrow_csr_scale; None is the factor 1."""
+        if r is None and c0 is None and c1 is None:
+            return
+        csr, rows = self._block_coo(block)
+        cols = csr.indices.astype(np.int64)
+        pos = cols >= 0
+        rf = r.numpy()[rows] if r is not None else 1.0
+        cf = np.ones(cols.size, dtype=np.float64)
+        if c0 is not None:
+            cf[pos] = c0.numpy()[cols[pos]]
+        if c1 is not None:
+            cf[~pos] = c1.numpy()[-cols[~pos] - 1]
+        csr.data[:] = ((csr.data.astype(np.float64) * rf) * cf).astype(
+            csr.data.dtype)
+
     def synchronize(self):
         pass
 
@@ -218,6 +270,34 @@ class GpuBackend:
     def norm_acc(self) -> torch.Tensor:
         """The two-double device accumulator of the step norms."""
         return torch.zeros(2, dtype=torch.float64, device=self.torch_device)
+
+    # -- operator scaling (arrow_csr_sums / arrow_csr_scale) ----------------
+
+    def scale_vector(self, x) -> torch.Tensor:
+        """A float64 device vector of the operator passes."""
+        return torch.from_numpy(np.array(x, dtype=np.float64)).to(
+            self.torch_device)
+
+    def _vec_ptr(self, v) -> int:
+        if v is None:
+            return 0
+        assert v.dtype == torch.float64 and v.is_contiguous() \
+            and v.device == self.torch_device
+        return v.data_ptr()
+
+    def block_sums(self, block: hip.CsrBlockGPU, row_sum, col_sum0, col_sum1,
+                   absolute=False):
+        """ADD the sums of the resident values of block into float64 device
+        vectors (views are fine: a row vector starts at the block's first
+        output row). None skips an output."""
+        block.sums(self._vec_ptr(row_sum), self._vec_ptr(col_sum0),
+                   self._vec_ptr(col_sum1), absolute, self._stream())
+
+    def block_scale(self, block: hip.CsrBlockGPU, r, c0, c1):
+        """Rescale the resident values of block in place by float64 device
+        vectors; None is the factor 1."""
+        block.scale(self._vec_ptr(r), self._vec_ptr(c0), self._vec_ptr(c1),
+                    self._stream())
 
     def axpby_rows(self, C: torch.Tensor, R, alpha: float, gamma: float):
         """C = alpha * C + gamma * R in place (arrow_axpby_rows_*)."""

@@ -47,7 +47,7 @@
 
 #include "../../include/arrow_spmm.h"
 
-#define ARROW_ABI_VERSION 1006  // step norms (arrow_spmm*_affine_norm*, arrow_diffnorm_rows_*)
+#define ARROW_ABI_VERSION 1007  // operator scaling (arrow_csr_sums, arrow_csr_scale)
 
 namespace {
 
@@ -232,6 +232,18 @@ template <> struct Prec<float> : PrecSame<float> {
   __device__ static __forceinline__ float mad(float a, float b, float c) {
     return fmaf(a, b, c);
   }
+  // a lane's own staged nonzero, no shuffle (the operator passes below), and
+  // the write-back of a rescaled value: the whole pair, one coalesced 8 B
+  __device__ static __forceinline__ int32_t own_col(const Staged &mine) {
+    return mine.x;
+  }
+  __device__ static __forceinline__ float own_val(const Staged &mine) {
+    return __int_as_float(mine.y);
+  }
+  __device__ static __forceinline__ void store_val(int32_t idx, int32_t col,
+                                                   float v, int2 *pairs) {
+    pairs[idx] = int2{col, __float_as_int(v)};
+  }
   template <typename F> static int with_stream(const CsrBlock &blk, F f) {
     return f(blk.pairs);
   }
@@ -267,6 +279,17 @@ template <> struct Prec<double> : PrecSame<double> {
   }
   __device__ static __forceinline__ double mad(double a, double b, double c) {
     return fma(a, b, c);
+  }
+  __device__ static __forceinline__ int32_t own_col(const Staged &mine) {
+    return mine.c;
+  }
+  __device__ static __forceinline__ double own_val(const Staged &mine) {
+    return __hiloint2double(mine.hi, mine.lo);
+  }
+  __device__ static __forceinline__ void store_val(int32_t idx, int32_t,
+                                                   double v, int32_t *,
+                                                   double *vals) {
+    vals[idx] = v;
   }
   template <typename F> static int with_stream(const CsrBlock &blk, F f) {
     return f(blk.cols64, blk.vals64);
@@ -1189,6 +1212,131 @@ int launch_axpby(const char *who, T *C, const T *R, int64_t n, int64_t k,
 }
 
 // ---------------------------------------------------------------------------
+// Operator passes over the resident values (arrow_csr_sums, arrow_csr_scale):
+// one streaming read (scale: and write) of the A stream, indexed exactly as
+// the SpMM launches index C / R (output row of the item), X0 (col >= 0) and
+// X1 (col < 0, at -col-1). One WAVE per work item, lanes strided over the
+// item's nonzeros, so the fp32 pairs and the f64 cols / vals are read and
+// written coalesced; waves stride over the items (the item index is
+// wave-uniform, so every lane of a wave reaches every shuffle). Written once
+// over the element type; A... is the mutable or const stream of Prec<T>.
+// ---------------------------------------------------------------------------
+
+constexpr int OPERATOR_MAX_BLOCKS = 4096;
+constexpr int WAVES_PER_BLOCK = BLOCK_THREADS / 64;
+
+// row_sum[out_row] += sum f(v), col_sum0[c] += f(v) (c >= 0),
+// col_sum1[-c-1] += f(v) (c < 0); f = fabs when absolute. All in double. A
+// null output is skipped. The row sum is reduced over the wave and added
+// with one float64 atomic per item (a split row has several items); the
+// column sums take one float64 hardware atomic per nonzero.
+template <typename T, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void csr_sums_kernel(
+    const int32_t *__restrict__ item_row,
+    const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end, int64_t n_items, double *row_sum,
+    double *col_sum0, double *col_sum1, int absolute,
+    const A *__restrict__... a) {
+  using P = Prec<T>;
+  const int lane = threadIdx.x & 63;
+  const int64_t n_waves = (int64_t)gridDim.x * WAVES_PER_BLOCK;
+  for (int64_t it = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+       it < n_items; it += n_waves) {
+    const int32_t row = item_row[it] & INT32_MAX;
+    const int32_t b = item_begin[it], e = item_end[it];
+    double s = 0.0;
+    for (int32_t t = b + lane; t < e; t += 64) {
+      const auto mine = P::load(0, t, a...);
+      const int32_t c = P::own_col(mine);
+      double v = (double)P::own_val(mine);
+      if (absolute) v = fabs(v);
+      s += v;
+      if (c >= 0) {
+        if (col_sum0) atomicAdd(col_sum0 + c, v);
+      } else {
+        if (col_sum1) atomicAdd(col_sum1 + -(c + 1), v);
+      }
+    }
+    if (row_sum) {  // kernel-uniform
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+      if (lane == 0 && e > b) atomicAdd(row_sum + row, s);
+    }
+  }
+}
+
+// val = (T)(((double)val * r) * c): r = row_scale[out_row], loaded once per
+// item, c = col_scale0[col] or col_scale1[-col-1]; a null vector is the
+// factor 1. Two double multiplies in this order, one rounding to T.
+template <typename T, typename... A>
+__global__ __launch_bounds__(BLOCK_THREADS) void csr_scale_kernel(
+    const int32_t *__restrict__ item_row,
+    const int32_t *__restrict__ item_begin,
+    const int32_t *__restrict__ item_end, int64_t n_items,
+    const double *__restrict__ row_scale, const double *col_scale0,
+    const double *col_scale1, A *__restrict__... a) {
+  using P = Prec<T>;
+  const int lane = threadIdx.x & 63;
+  const int64_t n_waves = (int64_t)gridDim.x * WAVES_PER_BLOCK;
+  for (int64_t it = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+       it < n_items; it += n_waves) {
+    const int32_t b = item_begin[it], e = item_end[it];
+    if (b >= e) continue;  // wave-uniform; no shuffle below
+    const double r =
+        row_scale ? row_scale[item_row[it] & INT32_MAX] : 1.0;
+    for (int32_t t = b + lane; t < e; t += 64) {
+      const auto mine = P::load(0, t, a...);
+      const int32_t c = P::own_col(mine);
+      double cf = 1.0;
+      if (c >= 0) {
+        if (col_scale0) cf = col_scale0[c];
+      } else {
+        if (col_scale1) cf = col_scale1[-(c + 1)];
+      }
+      const double v = ((double)P::own_val(mine) * r) * cf;
+      P::store_val(t, c, (T)v, a...);
+    }
+  }
+}
+
+inline int operator_blocks(const CsrBlock &blk) {
+  return (int)std::min<int64_t>(
+      (blk.n_items + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK,
+      OPERATOR_MAX_BLOCKS);
+}
+
+template <typename T>
+int launch_csr_sums(const CsrBlock &blk, double *row_sum, double *col_sum0,
+                    double *col_sum1, int absolute, hipStream_t stream) {
+  return Prec<T>::with_stream(blk, [&](auto *...a) {
+    hipLaunchKernelGGL(
+        (csr_sums_kernel<T, std::remove_pointer_t<decltype(a)>...>),
+        dim3(operator_blocks(blk)), dim3(BLOCK_THREADS), 0, stream,
+        (const int32_t *)blk.item_row, (const int32_t *)blk.item_begin,
+        (const int32_t *)blk.item_end, blk.n_items, row_sum, col_sum0,
+        col_sum1, absolute, a...);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  });
+}
+
+template <typename T>
+int launch_csr_scale(const CsrBlock &blk, const double *row_scale,
+                     const double *col_scale0, const double *col_scale1,
+                     hipStream_t stream) {
+  return Prec<T>::with_stream(blk, [&](auto *...a) {
+    hipLaunchKernelGGL(
+        (csr_scale_kernel<T, std::remove_pointer_t<decltype(a)>...>),
+        dim3(operator_blocks(blk)), dim3(BLOCK_THREADS), 0, stream,
+        (const int32_t *)blk.item_row, (const int32_t *)blk.item_begin,
+        (const int32_t *)blk.item_end, blk.n_items, row_scale, col_scale0,
+        col_scale1, a...);
+    HIP_CHECK(hipGetLastError());
+    return 0;
+  });
+}
+
+// ---------------------------------------------------------------------------
 // Row gather / scatter / scatter-add (permutation routing on-device).
 // ---------------------------------------------------------------------------
 
@@ -2087,6 +2235,48 @@ int arrow_csr_set_qblocks(int64_t handle, int blocks) {
   }
   it->second.q_blocks = blocks > 0 ? blocks : 0;
   return 0;
+}
+
+// ABI 1007: sums and in-place rescale of the resident values. Both dispatch
+// on the handle's precision tag; neither allocates nor reads on the host.
+int arrow_csr_sums(int64_t handle, double *row_sum_dev, double *col_sum0_dev,
+                   double *col_sum1_dev, int absolute, void *stream_v) {
+  if (!row_sum_dev && !col_sum0_dev && !col_sum1_dev) {
+    set_error("arrow_csr_sums: row_sum, col_sum0 and col_sum1 are all NULL");
+    return -7;
+  }
+  auto it = g_blocks.find(handle);
+  if (it == g_blocks.end()) {
+    set_error("arrow_csr_sums: bad handle");
+    return -1;
+  }
+  const CsrBlock &blk = it->second;
+  if (blk.nnz == 0) return 0;
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  return blk.dtype == 64
+             ? launch_csr_sums<double>(blk, row_sum_dev, col_sum0_dev,
+                                       col_sum1_dev, absolute, stream)
+             : launch_csr_sums<float>(blk, row_sum_dev, col_sum0_dev,
+                                      col_sum1_dev, absolute, stream);
+}
+
+int arrow_csr_scale(int64_t handle, const double *row_scale_dev,
+                    const double *col_scale0_dev, const double *col_scale1_dev,
+                    void *stream_v) {
+  auto it = g_blocks.find(handle);
+  if (it == g_blocks.end()) {
+    set_error("arrow_csr_scale: bad handle");
+    return -1;
+  }
+  const CsrBlock &blk = it->second;
+  if (blk.nnz == 0) return 0;
+  if (!row_scale_dev && !col_scale0_dev && !col_scale1_dev) return 0;
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  return blk.dtype == 64
+             ? launch_csr_scale<double>(blk, row_scale_dev, col_scale0_dev,
+                                        col_scale1_dev, stream)
+             : launch_csr_scale<float>(blk, row_scale_dev, col_scale0_dev,
+                                       col_scale1_dev, stream);
 }
 
 int arrow_spmm_dual(int64_t handle, const float *X0_dev, const float *X1_dev,

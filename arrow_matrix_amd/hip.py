@@ -69,6 +69,8 @@ def _load():
     #   ABI 1005  affine step: arrow_spmm[_dual]_affine*, arrow_axpby_rows_*
     #   ABI 1006  step norms: arrow_spmm[_dual]_affine_norm*,
     #             arrow_diffnorm_rows_*
+    #   ABI 1007  operator scaling: arrow_csr_sums, arrow_csr_scale (float32
+    #             and float64 handles; float64 device vectors in both)
     i64, cint, ptr, dbl = (ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
                           ctypes.c_double)
 
@@ -79,6 +81,9 @@ def _load():
         i64, i64, i64, ctypes.POINTER(i64), ctypes.POINTER(ctypes.c_int32),
         ctypes.POINTER(dbl), ctypes.POINTER(i64), cint], restype=i64)
     declare('arrow_csr_dtype', [i64])
+    # (handle, row, col0, col1, absolute, stream) / (handle, r, c0, c1, stream)
+    declare('arrow_csr_sums', [i64, ptr, ptr, ptr, cint, ptr])
+    declare('arrow_csr_scale', [i64, ptr, ptr, ptr, ptr])
     for sfx in _SPMM_SUFFIX.values():
         for dual in (False, True):
             for tier in _SPMM_TIERS:
@@ -279,6 +284,27 @@ class CsrBlockGPU:
         arrow_spmm_dual_affine_norm*)."""
         self._spmm((X0_ptr, X1_ptr), C_ptr, k, beta, stream, feat_dtype, alpha,
                    gamma, R_ptr, norm)
+
+    def sums(self, row_sum_ptr: int = 0, col_sum0_ptr: int = 0,
+             col_sum1_ptr: int = 0, absolute: bool = False, stream: int = 0):
+        """ADD the sums of the resident values into float64 device vectors
+        (arrow_csr_sums): row_sum by output row, as C; col_sum0 by column
+        c >= 0, as X0; col_sum1 at -c-1 for c < 0, as X1. absolute sums |v|.
+        A pointer of 0 skips that output; all three 0 is an error."""
+        _check(_load().arrow_csr_sums(
+            self._handle, row_sum_ptr or None, col_sum0_ptr or None,
+            col_sum1_ptr or None, 1 if absolute else 0, stream),
+            "arrow_csr_sums")
+
+    def scale(self, row_scale_ptr: int = 0, col_scale0_ptr: int = 0,
+              col_scale1_ptr: int = 0, stream: int = 0):
+        """Rescale the resident values in place (arrow_csr_scale):
+        val = T((float64(val) * r) * c), r and c from float64 device vectors
+        indexed as in sums; a pointer of 0 is the factor 1. Must not overlap
+        in time with an SpMM on this structure."""
+        _check(_load().arrow_csr_scale(
+            self._handle, row_scale_ptr or None, col_scale0_ptr or None,
+            col_scale1_ptr or None, stream), "arrow_csr_scale")
 
     def __del__(self):
         if getattr(self, '_handle', None) is not None and _lib is not None:

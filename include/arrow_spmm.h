@@ -451,6 +451,49 @@ int arrow_diffnorm_rows_bf16(const uint16_t *C_dev, const uint16_t *D_dev,
                              int64_t n, int64_t k, double *acc_dev,
                              void *stream);
 
+/* ---------------------------------------------------------------------
+ * Operator scaling (ABI 1007). The loops of the affine step converge only
+ * on a normalised operator: PageRank wants the column-stochastic A D^-1,
+ * random-walk diffusion D^-1 A, GCN / APPNP D^-1/2 A D^-1/2. The reference
+ * has no such call (its callers normalise the scipy matrix before they
+ * decompose it); here the RESIDENT values are summed, and rescaled in
+ * place as A <- diag(r) A diag(c), in one streaming pass each, with no
+ * re-upload.
+ *
+ * Indexing, the same in both calls and the same as in the SpMM launches:
+ * a row vector is indexed by OUTPUT row (after row_ids), as C and R are; a
+ * column index c >= 0 indexes the *0 vector, as X0; c < 0 indexes the *1
+ * vector at -c-1, as X1. The *1 vector may be the *0 vector. All vectors
+ * are doubles in device memory, in every precision; the caller sizes them
+ * as it sizes C, X0 and X1.
+ *
+ * arrow_csr_sums ADDS into its outputs (the caller zeroes them, so several
+ * structures can share one vector): with f(v) = v, or |v| when absolute is
+ * not 0, row_sum[row] += f(v), col_sum0[c] += f(v) or col_sum1[-c-1] +=
+ * f(v), for every stored nonzero. All summation is double. A NULL output is
+ * skipped; all three NULL is refused.
+ *
+ * arrow_csr_scale rewrites every stored value as
+ *     val = (T)(((double)val * r) * c)
+ * with r = row_scale[row], c the column factor, T the structure's
+ * precision: two double multiplies in this order, ONE rounding to T (a
+ * plain cast). A NULL vector is the factor 1; all three NULL returns 0 and
+ * launches nothing.
+ *
+ * Both take float32 and float64 handles (bf16 features share the float32
+ * structure) and leave work items, split table, queue segments and launch
+ * plan untouched. A bad handle returns a negative code, sets
+ * arrow_last_error() and launches nothing; nnz == 0 is a no-op returning
+ * 0. Neither allocates nor reads on the host: both are legal under stream
+ * capture. A SCALE MUST NOT OVERLAP IN TIME WITH AN SpMM, A SUMS OR ANOTHER
+ * SCALE ON THE SAME STRUCTURE (order them on one stream, or synchronise).
+ * ------------------------------------------------------------------- */
+int arrow_csr_sums(int64_t handle, double *row_sum_dev, double *col_sum0_dev,
+                   double *col_sum1_dev, int absolute, void *stream);
+int arrow_csr_scale(int64_t handle, const double *row_scale_dev,
+                    const double *col_scale0_dev, const double *col_scale1_dev,
+                    void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,12 +53,28 @@ def main() -> None:
                              '||X_new|| is <= T, and print the steps taken '
                              '(default: off, all -z iterations run)')
 
+    parser.add_argument('--normalize', choices=('row', 'col', 'sym'),
+                        default=None,
+                        help='normalise the loaded matrix on the device before '
+                             'the first step: row (D^-1 A), col (A D^-1, '
+                             'PageRank) or sym (D^-1/2 A D^-1/2); default: off')
+    parser.add_argument('--normalize-abs', action='store_true',
+                        help='with --normalize: use the sums of |a_ij|')
+
     args = vars(parser.parse_args())
     # off: the printed arguments and the run are what they were without them
     damping = args.pop('damping')
     tol = args.pop('tol')
+    normalize = args.pop('normalize')
+    normalize_abs = args.pop('normalize_abs')
     if tol is not None and damping is None:
         parser.error('--tol needs --damping')
+    if normalize_abs and normalize is None:
+        parser.error('--normalize-abs needs --normalize')
+    if normalize is not None:
+        args['normalize'] = normalize
+        if normalize_abs:
+            args['normalize_abs'] = True
     if damping is not None:
         args['damping'] = damping
     if tol is not None:
@@ -85,7 +101,10 @@ def main() -> None:
                            npy_format=args['npy'],
                            **({} if damping is None
                               else {'damping': damping}),
-                           **({} if tol is None else {'tol': tol}))
+                           **({} if tol is None else {'tol': tol}),
+                           **({} if normalize is None
+                              else {'normalize': normalize,
+                                    'normalize_abs': normalize_abs}))
 
 
 if __name__ == '__main__':
