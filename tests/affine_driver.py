@@ -3,59 +3,57 @@ GPU, in a process of its own: `python tests/affine_driver.py <precision>
 <environment>`, with precision f32, f64 or bf16 and an environment of
 spmm_cases_affine.ENVS.
 
-As in tests/spmm_driver.py (whose guarded buffers and Precision records this
-module imports), the ARROW_* kernel variables are read once per process, so
-the child STARTS with its environment; the scheduler and store form the
-launch plan reports are asserted before every launch; one JSON line is
-printed per case and the process exits non-zero on the first mismatch.
+Built on tests/child_harness.py (the job loop, the refusal check, the guarded
+buffers, the upload) and the Precision records of tests/spmm_driver.py. The
+ARROW_* kernel variables are read once per process, so the child STARTS with
+its environment; the scheduler and store form the launch plan reports are
+asserted before every launch; one JSON line is printed per case and the
+process exits non-zero on the first mismatch.
 
 Per launch: the sentinels around C and around R are intact, R keeps its bits,
 X is surrounded by NaN, rows outside row_ids keep their fill, and the result
 equals the float64 reference bit for bit (exact class) or to the derived
 bound (real class). This is a plain module, not a test file.
 """
-import json
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from arrow_matrix_amd import hip  # noqa: E402
 from tests import spmm_cases as sc  # noqa: E402
 from tests import spmm_cases_affine as sa  # noqa: E402
 from tests import spmm_driver as sd  # noqa: E402
-from tests.spmm_driver import Mismatch  # noqa: E402
+from tests.child_harness import Mismatch  # noqa: E402
 
 R_GUARD = {'f32': 0x5eed5eed, 'f64': 0x5eed5eed, 'bf16': 0x5eed}
-SUFFIX = {'f32': '', 'f64': '_f64', 'bf16': '_bf16'}
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+def tier_call(prec, tier, blk, xs, C, R, D, acc, k, alpha, gamma, beta):
+    """The entry point of the precision and tier ('_affine', '_affine_norm')
+    itself, through ctypes, on device addresses or None (the binding's spmm /
+    spmm_dual route (1, 0, NULL) to the plain entry point). Returns (rc,
+    message)."""
+    lib = hip._load()
+    fn = getattr(lib, hip._spmm_symbol(len(xs) == 2, tier,
+                                       hip._SPMM_SUFFIX[prec.name]))
+    rc = fn(*hip._spmm_args(tier, blk._handle, xs, C, R, D, acc, k, alpha,
+                            gamma, beta, ch.stream()))
+    return rc, lib.arrow_last_error().decode()
+
+
+def ptr(view):
+    return view.data_ptr() if view is not None else None
 
 
 def affine_call(prec, blk, dual, X0v, X1v, cv, Rv, k, alpha, gamma, beta):
-    """The affine entry point of the precision, through ctypes (the binding's
-    spmm / spmm_dual route (1, 0, NULL) to the plain entry point). Returns
-    (rc, message)."""
-    lib = hip._load()
-    sfx = SUFFIX[prec.name]
-    r = Rv.data_ptr() if Rv is not None else None
-    if dual:
-        rc = getattr(lib, 'arrow_spmm_dual_affine' + sfx)(
-            blk._handle, X0v.data_ptr(), X1v.data_ptr(), cv.data_ptr(), r, k,
-            alpha, gamma, beta, _stream())
-    else:
-        rc = getattr(lib, 'arrow_spmm_affine' + sfx)(
-            blk._handle, X0v.data_ptr(), cv.data_ptr(), r, k, alpha, gamma,
-            beta, _stream())
-    return rc, lib.arrow_last_error().decode()
+    xs = (ptr(X0v), ptr(X1v)) if dual else (ptr(X0v),)
+    return tier_call(prec, '_affine', blk, xs, ptr(cv), ptr(Rv), None, None,
+                     k, alpha, gamma, beta)
 
 
 _blocks = {}
@@ -66,17 +64,8 @@ def block(prec, case):
     key = (case['matrix'], case['kind'], bool(case.get('row_ids')),
            case.get('col_items', 0), case['queue'], case.get('qblocks', 0))
     if key not in _blocks:
-        m = sc.matrix(case['matrix'])
-        blk = hip.CsrBlockGPU(
-            arrays=((m['rows'], m['n0']), m['indptr'], m['cols'],
-                    prec.a_values(case, m)),
-            row_ids=sc.row_ids(case), col_items=case.get('col_items', 0),
-            dtype=prec.struct_dtype)
-        prec.check_block(blk)
-        blk.set_queue(case['queue'])
-        if case.get('qblocks'):
-            blk.set_qblocks(case['qblocks'])
-        _blocks[key] = blk
+        assert case['queue'] is not None    # every case here sets it
+        _blocks[key] = ch.upload(prec, case)
     return _blocks[key]
 
 
@@ -103,9 +92,12 @@ def shared(prec, case):
     return _shared[key]
 
 
-def run_case(prec, env, case):
+def checked_plan(prec, env, case):
+    """Before a launch: the plan reports the scheduler and store form the
+    environment selects, and the matrix has the rows the case is about.
+    Returns (matrix, plan, row lengths)."""
     m = sc.matrix(case['matrix'])
-    k, beta = case['k'], case['beta']
+    k = case['k']
     plan = hip.spmm_plan(k, int(m['cols'].size), case['queue'],
                          dtype=prec.plan_dtype)
     want = sa.expected_scheduler(env, case['queue'], plan['group'])
@@ -116,7 +108,12 @@ def run_case(prec, env, case):
         assert (lens > sc.SEG_NNZ).any()
     if case.get('init_capped'):
         assert (lens > sc.SEG_NNZ).sum() * k > 4096 * 256
+    return m, plan, lens
 
+
+def run_case(prec, env, case):
+    m, plan, lens = checked_plan(prec, env, case)
+    k, beta = case['k'], case['beta']
     X0, X1, C0, R, P, absP, X0v, X1v = shared(prec, case)
     rows, ref = sa.reference(prec.name, case, X0, X1, C0, R, product=P)
     untouched = np.setdiff1d(np.arange(C0.shape[0]), rows)
@@ -154,7 +151,7 @@ def run_case(prec, env, case):
             fn = blk.spmm_dual if m['n1'] else blk.spmm
             xs = (X0v.data_ptr(), X1v.data_ptr()) if m['n1'] \
                 else (X0v.data_ptr(),)
-            fn(*xs, cv.data_ptr(), k, beta, _stream(),
+            fn(*xs, cv.data_ptr(), k, beta, ch.stream(),
                feat_dtype=prec.feat_dtype)
             torch.cuda.synchronize()
             if not (sd.host_bits(prec, cv, C0_bits.shape) == got).all():
@@ -172,45 +169,38 @@ def run_case(prec, env, case):
 # misuse
 # ---------------------------------------------------------------------------
 
+def draw_bits(prec, rng, rows, k):
+    """The raw bits of a rows x k operand of small integers."""
+    return prec.bits(rng.integers(-8, 9, (rows, k)).astype(
+        np.float64 if prec.name == 'f64' else np.float32))
+
+
 def run_misuse(prec, env):
     """Each broken rule: a negative code, a message naming it, C unchanged
     (nothing is launched)."""
-    m = sc.matrix('std')
-    arrays = ((m['rows'], m['n0']), m['indptr'], m['cols'], m['vals'])
-    own = hip.CsrBlockGPU(arrays=arrays, dtype=prec.struct_dtype)
-    other = hip.CsrBlockGPU(
-        arrays=arrays,
-        dtype=np.float32 if prec.struct_dtype == np.float64 else np.float64)
+    m, own, other = ch.own_and_other(prec)
     rng = np.random.default_rng(1005)
-
-    def refused(blk, k, alpha, gamma, beta, R, words):
-        draw = lambda rows: prec.bits(
-            rng.integers(-8, 9, (rows, k)).astype(
-                np.float64 if prec.name == 'f64' else np.float32))
-        C0 = draw(m['rows'])
-        _, Xv = sd.guarded(prec, draw(m['n0']), prec.x_guard, 'cuda')
+    # (handle, k, beta, R, words), at alpha 0.5 and gamma 2.0
+    rules = [(blk, 8, beta, R, words) for beta in (0, 1)
+             for blk, R, words in (
+                 (own, 'null', ('R is NULL', 'gamma')),
+                 (own, 'c', ('R must not be C',)),
+                 (other, 'ok', ('float32', 'float64')))]
+    rules.append((own, 8, 2, 'ok', ('beta', '2')))
+    if prec.name == 'bf16':
+        rules.append((own, 12, 0, 'ok', ('k % 8', '12')))
+    for blk, k, beta, R, words in rules:
+        C0 = draw_bits(prec, rng, m['rows'], k)
+        _, Xv = sd.guarded(prec, draw_bits(prec, rng, m['n0'], k),
+                           prec.x_guard, 'cuda')
         cbuf, cv = sd.guarded(prec, C0, prec.c_guard, 'cuda')
-        _, Rv = sd.guarded(prec, draw(m['rows']), R_GUARD[prec.name], 'cuda')
+        _, Rv = sd.guarded(prec, draw_bits(prec, rng, m['rows'], k),
+                           R_GUARD[prec.name], 'cuda')
         Rarg = {'null': None, 'c': cv, 'ok': Rv}[R]
         for dual in (False, True):
-            rc, msg = affine_call(prec, blk, dual, Xv, Xv, cv, Rarg, k, alpha,
-                                  gamma, beta)
-            torch.cuda.synchronize()
-            if not rc < 0:
-                raise Mismatch(f"misuse accepted: {words} (rc {rc})")
-            if not all(w in msg for w in words):
-                raise Mismatch(f"message does not name {words}: {msg!r}")
-            if not (sd.guards_intact(cbuf, prec.c_guard)
-                    and (sd.host_bits(prec, cv, C0.shape) == C0).all()):
-                raise Mismatch(f"C was written by a refused call: {words}")
-
-    for beta in (0, 1):
-        refused(own, 8, 0.5, 2.0, beta, 'null', ('R is NULL', 'gamma'))
-        refused(own, 8, 0.5, 2.0, beta, 'c', ('R must not be C',))
-        refused(other, 8, 0.5, 2.0, beta, 'ok', ('float32', 'float64'))
-    refused(own, 8, 0.5, 2.0, 2, 'ok', ('beta', '2'))
-    if prec.name == 'bf16':
-        refused(own, 12, 0.5, 2.0, 0, 'ok', ('k % 8', '12'))
+            ch.refused(lambda: affine_call(prec, blk, dual, Xv, Xv, cv, Rarg,
+                                           k, 0.5, 2.0, beta),
+                       words, {'C': (cbuf, cv, prec.c_guard, C0)})
     return dict(sentinels='intact')
 
 
@@ -225,7 +215,7 @@ def run_axpby(prec, n, k, pair):
     cbuf, cv = sd.guarded(prec, C0_bits, prec.c_guard, 'cuda')
     rbuf, Rv = sd.guarded(prec, R_bits, R_GUARD[prec.name], 'cuda')
     hip.axpby_rows(cv.data_ptr(), Rv.data_ptr() if has_R else 0, n, k, alpha,
-                   gamma, _stream(), dtype=prec.route_dtype)
+                   gamma, ch.stream(), dtype=prec.route_dtype)
     torch.cuda.synchronize()
     if not sd.guards_intact(cbuf, prec.c_guard):
         raise Mismatch("sentinels around C were overwritten")
@@ -256,10 +246,8 @@ def job_names(prec_name, env):
 
 def main(argv):
     prec, env = sd.PRECISIONS[argv[1]], argv[2]
-    for var in sc.KERNEL_VARS:      # started with exactly this entry's set
-        assert os.environ.get(var) == sa.ENVS[env].get(var), var
-    assert torch.cuda.is_available(), "the affine driver needs a HIP GPU"
-    hip.set_device(torch.cuda.current_device())
+    ch.started_with(sc.KERNEL_VARS, sa.ENVS[env])
+    ch.open_gpu("the affine driver needs a HIP GPU")
 
     jobs = [(c['name'], lambda c=c: run_case(prec, env, c))
             for c in sa.gpu_cases(prec.name, env)]
@@ -267,19 +255,7 @@ def main(argv):
         jobs += [(name, lambda n=n, k=k, pair=pair: run_axpby(prec, n, k, pair))
                  for name, n, k, pair in axpby_jobs(prec)]
         jobs.append(('misuse', lambda: run_misuse(prec, env)))
-    for name, job in jobs:
-        line = {'case': name, 'env': env}
-        t0 = time.perf_counter()
-        try:
-            line.update(job())
-            line['ok'] = True
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        line['ms'] = round(1e3 * (time.perf_counter() - t0), 1)
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+    return ch.run_jobs(jobs, {'env': env})
 
 
 if __name__ == '__main__':

@@ -2,8 +2,9 @@
 entry point: `python tests/engine_affine_driver.py <mode>` runs one entry of
 MODES, in float32, float64 and bfloat16 features, in a process whose
 environment selects the engine layout (ARROW_FUSE_ALL / ARROW_FOLD are read
-when the structures are built), and prints one JSON line per precision. This
-is a plain module, not a test file.
+when the structures are built), and prints one JSON line per precision
+through the job loop of tests/child_harness.py. This is a plain module, not a
+test file.
 
 Step check. Three steps of X <- 0.85 A@X + 0.15 R; after each the golden is
 the float64 evaluation on the recomposed matrix of the engine's OWN previous
@@ -20,16 +21,15 @@ float64; for bfloat16 features s = L + 1: each part's launch rounds its
 contribution (or the running sum it adds to) once, and the layouts that
 finish with the tail kernel round once more. Derived, not measured.
 """
-import json
 import os
 import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from tests.gpu_children import ENGINE_VARS  # noqa: E402
 
@@ -161,38 +161,32 @@ def run(precision, **kwargs):
     return arrow, tails.calls, figures
 
 
+def run_mode(mode, precision):
+    """One precision of one entry of MODES; returns the line's figures."""
+    _, kwargs, inside = MODES[mode]
+    arrow, tails, figures = run(precision, **kwargs)
+    eng0 = arrow.engines[0]
+    # the path the environment asked for is the path that ran
+    if mode in ('fuse_all0', 'banded'):
+        assert eng0._A_all is None and eng0._A_row0 and eng0._A_rest
+        assert eng0.banded == (mode == 'banded')
+    elif mode == 'fold0':
+        assert arrow._folded is None
+    elif mode == 'fold1':
+        assert arrow._folded is not None and arrow._fold_cols
+    elif mode == 'fold2':
+        assert arrow._folded is not None and not arrow._fold_cols
+    # fused layouts never call the tail kernel; the others once a step
+    assert tails == (0 if inside else 3), f"{tails} tail calls"
+    return dict(tails=tails, max_err_over_bound=max(f[0] for f in figures))
+
+
 def main(argv):
     mode = argv[1]
-    variables, kwargs, inside = MODES[mode]
-    for var in ENGINE_VARS:         # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
-    import torch
-    assert torch.cuda.is_available(), "the affine engine driver needs a GPU"
-    for precision in PRECISIONS:
-        line = {'case': precision, 'mode': mode}
-        try:
-            arrow, tails, figures = run(precision, **kwargs)
-            eng0 = arrow.engines[0]
-            # the path the environment asked for is the path that ran
-            if mode in ('fuse_all0', 'banded'):
-                assert eng0._A_all is None and eng0._A_row0 and eng0._A_rest
-                assert eng0.banded == (mode == 'banded')
-            elif mode == 'fold0':
-                assert arrow._folded is None
-            elif mode == 'fold1':
-                assert arrow._folded is not None and arrow._fold_cols
-            elif mode == 'fold2':
-                assert arrow._folded is not None and not arrow._fold_cols
-            # fused layouts never call the tail kernel; the others once a step
-            assert tails == (0 if inside else 3), f"{tails} tail calls"
-            line.update(ok=True, tails=tails,
-                        max_err_over_bound=max(f[0] for f in figures))
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+    ch.started_with(ENGINE_VARS, MODES[mode][0])
+    ch.open_gpu("the affine engine driver needs a GPU", set_device=False)
+    return ch.run_jobs([(p, lambda p=p: run_mode(mode, p))
+                        for p in PRECISIONS], {'mode': mode})
 
 
 if __name__ == '__main__':

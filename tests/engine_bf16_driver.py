@@ -24,9 +24,9 @@ import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from tests.gpu_children import ENGINE_VARS  # noqa: E402
 
@@ -117,10 +117,8 @@ def run_bf16(**kwargs):
 def main(argv):
     mode, out = argv[1], argv[2]
     variables, kwargs = MODES[mode]
-    for var in ENGINE_VARS:         # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
-    import torch
-    assert torch.cuda.is_available(), "the bfloat16 engine driver needs a GPU"
+    ch.started_with(ENGINE_VARS, variables)
+    ch.open_gpu("the bfloat16 engine driver needs a GPU", set_device=False)
     results, goldens, bounds, arrow = run_bf16(**kwargs)
     eng0 = arrow.engines[0]
     # the path the environment asked for is the path that ran

@@ -10,9 +10,9 @@ import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from tests.gpu_children import ENGINE_VARS  # noqa: E402
 
@@ -96,10 +96,8 @@ def run_f64(n_blocks, width, k, seed, iters=1, device='gpu',
 def main(argv):
     mode, out = argv[1], argv[2]
     variables, kwargs = MODES[mode]
-    for var in ENGINE_VARS:         # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
-    import torch
-    assert torch.cuda.is_available(), "the float64 engine driver needs a GPU"
+    ch.started_with(ENGINE_VARS, variables)
+    ch.open_gpu("the float64 engine driver needs a GPU", set_device=False)
     results, goldens, _ = run_f64(**kwargs)
     np.save(out, np.stack([np.stack(results), np.stack(goldens)]))
     return 0

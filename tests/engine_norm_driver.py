@@ -3,7 +3,8 @@ entry point: `python tests/engine_norm_driver.py <mode>` runs one entry of
 MODES with and without an affine step, in float32, float64 and bfloat16
 features, in a process whose environment selects the engine layout, and
 prints one JSON line per (precision, affine). Built on
-tests/engine_affine_driver.py. This is a plain module, not a test file.
+tests/engine_affine_driver.py and the job loop of tests/child_harness.py. This
+is a plain module, not a test file.
 
 Per step: the tracked engine's result equals an untracked engine's bit for
 bit; the two accumulators are compared with the host's float64 sums over the
@@ -11,7 +12,6 @@ stripes as read back (the result, and the features before the step), to
 spmm_cases_norm.norm_bound; last_step_norms() is the square roots of the
 accumulators; and the backend's counters say which entry point measured.
 """
-import json
 import math
 import os
 import sys
@@ -19,9 +19,9 @@ import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from tests import engine_affine_driver as ead  # noqa: E402
 from tests import spmm_cases_norm as sn  # noqa: E402
@@ -145,40 +145,35 @@ def run_iterate(precision, device):
     return arrow.iterate(ITER_MAX, tol=ITER_TOL[precision])
 
 
+def run_mode(mode, precision, affine):
+    """One (precision, affine) of one entry of MODES; returns the line's
+    figures."""
+    _, kwargs, fused = MODES[mode]
+    arrow, n_fused, n_alone, worst = run_tracked(precision, affine, **kwargs)
+    eng0 = arrow.engines[0]
+    # the path the environment asked for is the path that ran
+    if mode == 'default':
+        assert eng0._A_all is not None
+    elif mode == 'fuse_all0':
+        assert eng0._A_all is None and eng0._A_row0
+    elif mode == 'fold0':
+        assert arrow._folded is None
+    elif mode == 'fold1':
+        assert arrow._folded is not None and arrow._fold_cols
+    elif mode == 'fold2':
+        assert arrow._folded is not None and not arrow._fold_cols
+    check_counters(fused, n_fused, n_alone)
+    return dict(fused_launches=n_fused, stand_alone=n_alone,
+                max_err_over_bound=worst)
+
+
 def main(argv):
     mode = argv[1]
-    variables, kwargs, fused = MODES[mode]
-    for var in ENGINE_VARS:         # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
-    import torch
-    assert torch.cuda.is_available(), "the norm engine driver needs a GPU"
-    for precision in PRECISIONS:
-        for affine in (False, True):
-            line = {'case': f'{precision}_affine{int(affine)}', 'mode': mode}
-            try:
-                arrow, n_fused, n_alone, worst = run_tracked(
-                    precision, affine, **kwargs)
-                eng0 = arrow.engines[0]
-                # the path the environment asked for is the path that ran
-                if mode == 'default':
-                    assert eng0._A_all is not None
-                elif mode == 'fuse_all0':
-                    assert eng0._A_all is None and eng0._A_row0
-                elif mode == 'fold0':
-                    assert arrow._folded is None
-                elif mode == 'fold1':
-                    assert arrow._folded is not None and arrow._fold_cols
-                elif mode == 'fold2':
-                    assert arrow._folded is not None and not arrow._fold_cols
-                check_counters(fused, n_fused, n_alone)
-                line.update(ok=True, fused_launches=n_fused,
-                            stand_alone=n_alone, max_err_over_bound=worst)
-            except AssertionError as e:
-                line.update(ok=False, error=str(e)[:2000])
-            print(json.dumps(line), flush=True)
-            if not line['ok']:
-                return 1
-    return 0
+    ch.started_with(ENGINE_VARS, MODES[mode][0])
+    ch.open_gpu("the norm engine driver needs a GPU", set_device=False)
+    return ch.run_jobs(
+        [(f'{p}_affine{int(a)}', lambda p=p, a=a: run_mode(mode, p, a))
+         for p in PRECISIONS for a in (False, True)], {'mode': mode})
 
 
 if __name__ == '__main__':

@@ -4,7 +4,8 @@ tests/engine_scale_driver.py <mode> <device>` runs one entry of MODES on the
 cpu or gpu device, in every precision the device has, in a process whose
 environment selects the engine layout (ARROW_FUSE_ALL / ARROW_FOLD are read
 when the structures are built), and prints one JSON line per precision. Built
-on tests/engine_affine_driver.py. This is a plain module, not a test file.
+on tests/engine_affine_driver.py and the job loop of tests/child_harness.py.
+This is a plain module, not a test file.
 
 The oracle is scipy on synth.recompose, indexed by perm0: vectors of the
 engine are in part 0's layout, as features are, so entry j belongs to
@@ -25,16 +26,15 @@ values, 2**-24 for float32 and bfloat16 features, 2**-53 for float64):
                   (u_T + (2 n_i + n_c + 8) 2**-53) S_i, the n_i of the check's
                   own sum included.
 """
-import json
 import os
 import sys
 import tempfile
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from tests import engine_affine_driver as ead  # noqa: E402
 from tests import engine_norm_driver as end  # noqa: E402
@@ -297,23 +297,12 @@ def run_mode(mode, device, precision):
 
 def main(argv):
     mode, device = argv[1], argv[2]
-    variables, _ = MODES[mode]
-    for var in ENGINE_VARS:         # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
+    ch.started_with(ENGINE_VARS, MODES[mode][0])
     if device == 'gpu':
-        import torch
-        assert torch.cuda.is_available(), "the scale engine driver needs a GPU"
-    for precision in PRECISIONS[device]:
-        line = {'case': precision, 'mode': mode, 'device': device}
-        try:
-            line.update(run_mode(mode, device, precision))
-            line['ok'] = True
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+        ch.open_gpu("the scale engine driver needs a GPU", set_device=False)
+    return ch.run_jobs([(p, lambda p=p: run_mode(mode, device, p))
+                        for p in PRECISIONS[device]],
+                       {'mode': mode, 'device': device})
 
 
 if __name__ == '__main__':

@@ -1,9 +1,10 @@
 """Runs the far-offset cases of one precision on the GPU, in a process of its
 own: `python tests/far_driver.py <precision>`, with precision f32, f64 or
 bf16 and no ARROW_* kernel variable set. The geometry, the case lists and the
-peak-memory figures are tests/spmm_cases_far.py's; the Precision records,
-guarded buffers, plan check and exact comparators are tests/spmm_driver.py's,
-the affine and norm calls tests/affine_driver.py's and tests/norm_driver.py's.
+peak-memory figures are tests/spmm_cases_far.py's; the job loop, the guarded
+buffers and the upload are tests/child_harness.py's, the Precision records,
+plan check and exact comparators tests/spmm_driver.py's, the entry-point call
+tests/affine_driver.py's, the accumulators tests/norm_driver.py's.
 
 Per case: the launch plan is asserted; the touched rows equal the compact
 reference bit for bit; the sentinels around every buffer are intact; a tall
@@ -17,16 +18,15 @@ failed case. This is a plain module, not a test file.
 """
 import ctypes
 import json
-import os
 import sys
 import time
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from arrow_matrix_amd import hip  # noqa: E402
 from tests import affine_driver as ad  # noqa: E402
@@ -34,7 +34,7 @@ from tests import norm_driver as nd  # noqa: E402
 from tests import spmm_cases as sc  # noqa: E402
 from tests import spmm_cases_far as far  # noqa: E402
 from tests import spmm_driver as sd  # noqa: E402
-from tests.spmm_driver import Mismatch  # noqa: E402
+from tests.child_harness import Mismatch  # noqa: E402
 
 assert far.PAD == sd.PAD
 
@@ -43,10 +43,6 @@ FORMULA_SLICE = 1 << 22        # elements per int64 formula slice (32 MiB)
 TORCH_DTYPE = {'f32': torch.float32, 'f64': torch.float64,
                'bf16': torch.bfloat16}
 BITS_DTYPE = {'f32': torch.int32, 'f64': torch.int64, 'bf16': torch.int16}
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ---------------------------------------------------------------------------
@@ -137,14 +133,9 @@ _blocks = {}
 def far_block(prec, case, m, pl):
     key = (case['role'], case['k'], case['queue'])
     if key not in _blocks:
-        cols = m['cols'] if pl['cols'] is None else pl['cols']
-        blk = hip.CsrBlockGPU(
-            arrays=((m['rows'], m['n0']), m['indptr'], cols,
-                    prec.a_values(case, m)),
-            row_ids=pl['row_ids'], dtype=prec.struct_dtype)
-        prec.check_block(blk)
-        blk.set_queue(case['queue'])
-        _blocks[key] = blk
+        if pl['cols'] is not None:
+            m = dict(m, cols=pl['cols'])
+        _blocks[key] = ch.upload(prec, case, m, row_ids=pl['row_ids'])
     return _blocks[key]
 
 
@@ -231,30 +222,26 @@ def run_spmm_case(prec, case, tall):
         rptr = None
 
     blk = far_block(prec, case, m, pl)
-    lib = hip._load()
-    sfx = ad.SUFFIX[prec.name]
     if entry == 'spmm':
         if dual:
-            blk.spmm_dual(x0p, x1p, cptr, k, beta, _stream(),
+            blk.spmm_dual(x0p, x1p, cptr, k, beta, ch.stream(),
                           feat_dtype=prec.feat_dtype)
         else:
-            blk.spmm(x0p, cptr, k, beta, _stream(),
+            blk.spmm(x0p, cptr, k, beta, ch.stream(),
                      feat_dtype=prec.feat_dtype)
         rc = 0
     else:
+        aptr = None
         if entry == 'norm':
             abuf, accv = nd.acc_buffer()
-            name, tail = 'affine_norm', (rptr, dptr, accv.data_ptr())
-        else:
-            name, tail = 'affine', (rptr,)
-        xs = (x0p, x1p) if dual else (x0p,)
-        rc = getattr(lib, f"arrow_spmm_{'dual_' if dual else ''}{name}{sfx}")(
-            blk._handle, *xs, cptr, *tail, k, case['alpha'], case['gamma'],
-            beta, _stream())
+            aptr = accv.data_ptr()
+        rc, msg = ad.tier_call(
+            prec, '_affine_norm' if entry == 'norm' else '_affine', blk,
+            (x0p, x1p) if dual else (x0p,), cptr, rptr, dptr, aptr, k,
+            case['alpha'], case['gamma'], beta)
     torch.cuda.synchronize()
     if rc != 0:
-        raise Mismatch(f"{entry} call failed ({rc}): "
-                       f"{lib.arrow_last_error().decode()}")
+        raise Mismatch(f"{entry} call failed ({rc}): {msg}")
 
     got = read_c()
     for what, check in checks:
@@ -267,7 +254,7 @@ def run_spmm_case(prec, case, tall):
             raise Mismatch("rows outside row_ids were written")
     info = dict(prec.exact(got[rows], ref, lens))
     if entry == 'norm':
-        if not nd.acc_guards_intact(abuf):
+        if not ch.f64_guards_intact(abuf):
             raise Mismatch("sentinels around the accumulators were "
                            "overwritten")
         info.update(nd.check_acc(prec, case, accv.cpu().numpy(),
@@ -308,14 +295,14 @@ def run_route_case(prec, op, k, side, tall):
     dt = dict(dtype=prec.route_dtype)
     if op == 'gather':
         hip.gather_rows(sptr, dptr, idx['src_idx'].data_ptr(), n, k,
-                        _stream(), **dt)
+                        ch.stream(), **dt)
     elif op in ('scatter', 'scatter_add'):
         fn = hip.scatter_rows if op == 'scatter' else hip.scatter_add_rows
-        fn(dptr, sptr, idx['dst_idx'].data_ptr(), n, k, _stream(), **dt)
+        fn(dptr, sptr, idx['dst_idx'].data_ptr(), n, k, ch.stream(), **dt)
     else:
         fn = hip.permute_rows if op == 'permute' else hip.permute_add_rows
         fn(dptr, sptr, idx['dst_idx'].data_ptr(), idx['src_idx'].data_ptr(),
-           n, k, _stream(), **dt)
+           n, k, ch.stream(), **dt)
     torch.cuda.synchronize()
     if not sd.guards_intact(dbuf, prec.c_guard):
         raise Mismatch("sentinels around dst were overwritten")
@@ -368,11 +355,11 @@ def run_contig_case(prec, kernel, n, k, tall):
     optr = view_ptr(prec, obuf) if second else 0
     if kernel == 'axpby':
         hip.axpby_rows(view_ptr(prec, cbuf), optr, n, k, alpha, gamma,
-                       _stream(), dtype=prec.route_dtype)
+                       ch.stream(), dtype=prec.route_dtype)
     else:
         abuf, accv = nd.acc_buffer()
         hip.diffnorm_rows(view_ptr(prec, cbuf), optr, n, k, accv.data_ptr(),
-                          _stream(), dtype=prec.route_dtype)
+                          ch.stream(), dtype=prec.route_dtype)
     torch.cuda.synchronize()
     for buf, guard in ((cbuf, prec.c_guard), (obuf, o_guard)):
         if buf is not None and not sd.guards_intact(buf, guard):
@@ -402,7 +389,7 @@ def run_contig_case(prec, kernel, n, k, tall):
                        "an input of the pass was written")
     info = dict(sentinels='intact', elements=total)
     if kernel == 'diffnorm':
-        if not nd.acc_guards_intact(abuf):
+        if not ch.f64_guards_intact(abuf):
             raise Mismatch("sentinels around the accumulators were "
                            "overwritten")
         want = tuple(float(s) for s in sums.tolist())
@@ -483,30 +470,29 @@ def jobs(prec, tall):
 def main(argv):
     prec = sd.PRECISIONS[argv[1]]
     only = argv[2:]          # job-name prefixes, for a run by hand
-    for var in sc.KERNEL_VARS:      # default kernel variables
-        assert os.environ.get(var) is None, var
-    assert torch.cuda.is_available(), "the far driver needs a HIP GPU"
-    hip.set_device(torch.cuda.current_device())
+    ch.started_with(sc.KERNEL_VARS, {})
+    ch.open_gpu("the far driver needs a HIP GPU")
 
     tall = Tall()
     t_start = time.perf_counter()
-    for name, group, job in jobs(prec, tall):
-        if only and not any(name.startswith(p) for p in only):
-            continue
-        line = {'case': name, 'prec': prec.name}
-        t0 = time.perf_counter()
-        tall.group(group)       # frees the last group's before the peak resets
-        torch.cuda.reset_peak_memory_stats()
-        try:
-            line.update(job())
-            line['ok'] = True
-        except Exception as e:      # an allocation that fails is a failure
-            line.update(ok=False, error=f"{type(e).__name__}: {e}"[:2000])
+    todo = [j for j in jobs(prec, tall)
+            if not only or any(j[0].startswith(p) for p in only)]
+    group_of = {name: group for name, group, _ in todo}
+
+    def before(name):
+        tall.group(group_of[name])  # frees the last group's before the
+        torch.cuda.reset_peak_memory_stats()    # peak resets
+
+    def after(line):
         line['peak_bytes'] = int(torch.cuda.max_memory_allocated())
-        line['ms'] = round(1e3 * (time.perf_counter() - t0), 1)
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
+
+    # an allocation that fails is a failed case, not an errored child
+    status = ch.run_jobs([(name, job) for name, _, job in todo],
+                         {'prec': prec.name},
+                         failed=(AssertionError, torch.cuda.OutOfMemoryError),
+                         before=before, after=after)
+    if status:
+        return status
     tall.free()
     print(json.dumps({'case': 'total', 'prec': prec.name, 'ok': True,
                       's': round(time.perf_counter() - t_start, 1)}),

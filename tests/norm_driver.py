@@ -1,8 +1,9 @@
 """Runs the step-norm kernel cases of one (precision, environment) on the GPU,
 in a process of its own: `python tests/norm_driver.py <precision>
 <environment>`, with precision f32, f64 or bf16 and an environment of
-spmm_cases_norm.ENVS. Built on tests/affine_driver.py (blocks, shared
-operands, the affine call) and tests/spmm_driver.py (guarded buffers).
+spmm_cases_norm.ENVS. Built on tests/child_harness.py (the job loop, the
+refusal check, the guarded buffers) and tests/affine_driver.py (blocks,
+shared operands, the plan check, the entry-point call).
 
 Per launch: the plan reports the scheduler the environment selects; C from
 the measuring entry point equals C from the affine entry point bit for bit
@@ -13,32 +14,24 @@ the device's OWN C and D as read back: bit for bit in the fp32 / bf16 exact
 class, to spmm_cases_norm.norm_bound otherwise. This is a plain module, not a
 test file.
 """
-import json
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from arrow_matrix_amd import hip  # noqa: E402
 from tests import affine_driver as ad  # noqa: E402
 from tests import spmm_cases as sc  # noqa: E402
 from tests import spmm_cases_norm as sn  # noqa: E402
 from tests import spmm_driver as sd  # noqa: E402
-from tests.spmm_driver import Mismatch  # noqa: E402
+from tests.child_harness import Mismatch  # noqa: E402
 
 D_GUARD = {'f32': 0x0d0d0d0d, 'f64': 0x0d0d0d0d, 'bf16': 0x0d0d}
-ACC_GUARD = -7.0     # around the two doubles
-ACC_PAD = 8
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+ACC_PAD = 8          # sentinels either side of the two doubles
 
 
 def values(prec, bits):
@@ -52,35 +45,16 @@ def values(prec, bits):
 
 def acc_buffer(init=(0.0, 0.0)):
     """(buffer, view): two doubles between ACC_PAD sentinels each side."""
-    buf = torch.full((2 + 2 * ACC_PAD,), ACC_GUARD, dtype=torch.float64,
-                     device='cuda')
-    view = buf[ACC_PAD:ACC_PAD + 2]
-    view.copy_(torch.tensor(init, dtype=torch.float64))
-    return buf, view
-
-
-def acc_guards_intact(buf):
-    h = buf.cpu().numpy()
-    return bool((h[:ACC_PAD] == ACC_GUARD).all()
-                and (h[-ACC_PAD:] == ACC_GUARD).all())
+    return ch.guarded_f64(init, ACC_PAD)
 
 
 def norm_call(prec, blk, dual, X0v, X1v, cv, Rv, Dv, accv, k, alpha, gamma,
               beta):
     """The measuring entry point of the precision, through ctypes. Returns
     (rc, message)."""
-    lib = hip._load()
-    sfx = ad.SUFFIX[prec.name]
-    ptr = lambda t: t.data_ptr() if t is not None else None
-    if dual:
-        rc = getattr(lib, 'arrow_spmm_dual_affine_norm' + sfx)(
-            blk._handle, X0v.data_ptr(), X1v.data_ptr(), cv.data_ptr(),
-            ptr(Rv), ptr(Dv), ptr(accv), k, alpha, gamma, beta, _stream())
-    else:
-        rc = getattr(lib, 'arrow_spmm_affine_norm' + sfx)(
-            blk._handle, X0v.data_ptr(), cv.data_ptr(), ptr(Rv), ptr(Dv),
-            ptr(accv), k, alpha, gamma, beta, _stream())
-    return rc, lib.arrow_last_error().decode()
+    xs = (ad.ptr(X0v), ad.ptr(X1v)) if dual else (ad.ptr(X0v),)
+    return ad.tier_call(prec, '_affine_norm', blk, xs, ad.ptr(cv), ad.ptr(Rv),
+                        ad.ptr(Dv), ad.ptr(accv), k, alpha, gamma, beta)
 
 
 def check_acc(prec, case, got_acc, c, d, calls=1):
@@ -102,19 +76,8 @@ def check_acc(prec, case, got_acc, c, d, calls=1):
 
 
 def run_case(prec, env, case):
-    m = sc.matrix(case['matrix'])
+    m, plan, lens = ad.checked_plan(prec, env, case)
     k = case['k']
-    plan = hip.spmm_plan(k, int(m['cols'].size), case['queue'],
-                         dtype=prec.plan_dtype)
-    want = sn.expected_scheduler(env, case['queue'], plan['group'])
-    if plan['scheduler'] != want or plan['nt_mode'] != (env != 'nt0'):
-        raise Mismatch(f"plan {plan}: expected scheduler {want}")
-    lens = np.diff(m['indptr'])
-    if case['matrix'] in ('std', 'std_dual', 'zero_rows'):
-        assert (lens > sc.SEG_NNZ).any()
-    if case.get('init_capped'):
-        assert (lens > sc.SEG_NNZ).sum() * k > 4096 * 256
-
     X0, X1, C0, R, P, absP, X0v, X1v = ad.shared(prec, case)
     rows, ref = ad.sa.reference(prec.name, case, X0, X1, C0, R, product=P)
     untouched = np.setdiff1d(np.arange(C0.shape[0]), rows)
@@ -161,7 +124,7 @@ def run_case(prec, env, case):
     got_acc = accv.cpu().numpy()
     if not sd.guards_intact(cbuf, prec.c_guard):
         raise Mismatch("sentinels around C were overwritten")
-    if not acc_guards_intact(abuf):
+    if not ch.f64_guards_intact(abuf):
         raise Mismatch("sentinels around the accumulators were overwritten")
     if dbuf is not None and not (
             sd.guards_intact(dbuf, D_GUARD[prec.name])
@@ -200,51 +163,37 @@ def run_case(prec, env, case):
 def run_misuse(prec, env):
     """Each broken rule: a negative code, a message naming it, C and the
     accumulators unchanged (nothing is launched)."""
-    m = sc.matrix('std')
-    arrays = ((m['rows'], m['n0']), m['indptr'], m['cols'], m['vals'])
-    own = hip.CsrBlockGPU(arrays=arrays, dtype=prec.struct_dtype)
-    other = hip.CsrBlockGPU(
-        arrays=arrays,
-        dtype=np.float32 if prec.struct_dtype == np.float64 else np.float64)
+    m, own, other = ch.own_and_other(prec)
     rng = np.random.default_rng(1006)
-
-    def refused(blk, k, gamma, beta, R, D, acc, words):
-        draw = lambda rows: prec.bits(
-            rng.integers(-8, 9, (rows, k)).astype(
-                np.float64 if prec.name == 'f64' else np.float32))
-        C0 = draw(m['rows'])
-        _, Xv = sd.guarded(prec, draw(m['n0']), prec.x_guard, 'cuda')
+    # (handle, k, beta, R, D, acc given, words), at alpha 0.5 and gamma 2.0
+    rules = [(own, 8, 0, 'ok', 'ok', False, ('acc is NULL',)),
+             (own, 8, 0, 'ok', 'c', True, ('D must not be C',)),
+             (own, 8, 1, 'ok', 'ok', True, ('beta must be 0', '1')),
+             (own, 8, 2, 'ok', 'ok', True, ('beta must be 0', '2')),
+             (own, 8, 0, 'null', 'ok', True, ('R is NULL', 'gamma')),
+             (own, 8, 0, 'c', 'ok', True, ('R must not be C',)),
+             (other, 8, 0, 'ok', 'ok', True, ('float32', 'float64'))]
+    if prec.name == 'bf16':
+        rules.append((own, 12, 0, 'ok', 'ok', True, ('k % 8', '12')))
+    for blk, k, beta, R, D, acc, words in rules:
+        C0 = ad.draw_bits(prec, rng, m['rows'], k)
+        _, Xv = sd.guarded(prec, ad.draw_bits(prec, rng, m['n0'], k),
+                           prec.x_guard, 'cuda')
         cbuf, cv = sd.guarded(prec, C0, prec.c_guard, 'cuda')
-        _, Rv = sd.guarded(prec, draw(m['rows']), ad.R_GUARD[prec.name],
-                           'cuda')
-        _, Dv = sd.guarded(prec, draw(m['rows']), D_GUARD[prec.name], 'cuda')
+        _, Rv = sd.guarded(prec, ad.draw_bits(prec, rng, m['rows'], k),
+                           ad.R_GUARD[prec.name], 'cuda')
+        _, Dv = sd.guarded(prec, ad.draw_bits(prec, rng, m['rows'], k),
+                           D_GUARD[prec.name], 'cuda')
         abuf, accv = acc_buffer((3.5, -2.25))
         Rarg = {'null': None, 'c': cv, 'ok': Rv}[R]
         Darg = {'c': cv, 'ok': Dv}[D]
         for dual in (False, True):
-            rc, msg = norm_call(prec, blk, dual, Xv, Xv, cv, Rarg, Darg,
-                                accv if acc else None, k, 0.5, gamma, beta)
-            torch.cuda.synchronize()
-            if not rc < 0:
-                raise Mismatch(f"misuse accepted: {words} (rc {rc})")
-            if not all(w in msg for w in words):
-                raise Mismatch(f"message does not name {words}: {msg!r}")
-            if not (sd.guards_intact(cbuf, prec.c_guard)
-                    and (sd.host_bits(prec, cv, C0.shape) == C0).all()):
-                raise Mismatch(f"C was written by a refused call: {words}")
-            if not (acc_guards_intact(abuf)
-                    and accv.cpu().tolist() == [3.5, -2.25]):
-                raise Mismatch(f"acc was written by a refused call: {words}")
-
-    refused(own, 8, 2.0, 0, 'ok', 'ok', False, ('acc is NULL',))
-    refused(own, 8, 2.0, 0, 'ok', 'c', True, ('D must not be C',))
-    refused(own, 8, 2.0, 1, 'ok', 'ok', True, ('beta must be 0', '1'))
-    refused(own, 8, 2.0, 2, 'ok', 'ok', True, ('beta must be 0', '2'))
-    refused(own, 8, 2.0, 0, 'null', 'ok', True, ('R is NULL', 'gamma'))
-    refused(own, 8, 2.0, 0, 'c', 'ok', True, ('R must not be C',))
-    refused(other, 8, 2.0, 0, 'ok', 'ok', True, ('float32', 'float64'))
-    if prec.name == 'bf16':
-        refused(own, 12, 2.0, 0, 'ok', 'ok', True, ('k % 8', '12'))
+            ch.refused(lambda: norm_call(prec, blk, dual, Xv, Xv, cv, Rarg,
+                                         Darg, accv if acc else None, k, 0.5,
+                                         2.0, beta),
+                       words, {'C': (cbuf, cv, prec.c_guard, C0),
+                               'acc': (abuf, accv, ch.F64_GUARD,
+                                       [3.5, -2.25])})
     return dict(sentinels='intact')
 
 
@@ -259,14 +208,14 @@ def run_diffnorm(prec, n, k, with_D):
     dbuf, Dv = sd.guarded(prec, D_bits, D_GUARD[prec.name], 'cuda')
     abuf, accv = acc_buffer()
     hip.diffnorm_rows(cv.data_ptr(), Dv.data_ptr() if with_D else 0, n, k,
-                      accv.data_ptr(), _stream(), dtype=prec.route_dtype)
+                      accv.data_ptr(), ch.stream(), dtype=prec.route_dtype)
     torch.cuda.synchronize()
     for buf, view, bits, guard in ((cbuf, cv, C_bits, prec.c_guard),
                                    (dbuf, Dv, D_bits, D_GUARD[prec.name])):
         if not (sd.guards_intact(buf, guard)
                 and (sd.host_bits(prec, view, bits.shape) == bits).all()):
             raise Mismatch("an input or the sentinels around it were written")
-    if not acc_guards_intact(abuf):
+    if not ch.f64_guards_intact(abuf):
         raise Mismatch("sentinels around the accumulators were overwritten")
     got = tuple(accv.cpu().tolist())
     # integers: exact in every precision, float64 included
@@ -295,10 +244,8 @@ def job_names(prec_name, env):
 
 def main(argv):
     prec, env = sd.PRECISIONS[argv[1]], argv[2]
-    for var in sc.KERNEL_VARS:      # started with exactly this entry's set
-        assert os.environ.get(var) == sn.ENVS[env].get(var), var
-    assert torch.cuda.is_available(), "the norm driver needs a HIP GPU"
-    hip.set_device(torch.cuda.current_device())
+    ch.started_with(sc.KERNEL_VARS, sn.ENVS[env])
+    ch.open_gpu("the norm driver needs a HIP GPU")
 
     jobs = [(c['name'], lambda c=c: run_case(prec, env, c))
             for c in sn.gpu_cases(prec.name, env)]
@@ -306,19 +253,7 @@ def main(argv):
         jobs += [(name, lambda n=n, k=k, w=w: run_diffnorm(prec, n, k, w))
                  for name, n, k, w in diffnorm_jobs(prec)]
         jobs.append(('misuse', lambda: run_misuse(prec, env)))
-    for name, job in jobs:
-        line = {'case': name, 'env': env}
-        t0 = time.perf_counter()
-        try:
-            line.update(job())
-            line['ok'] = True
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        line['ms'] = round(1e3 * (time.perf_counter() - t0), 1)
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+    return ch.run_jobs(jobs, {'env': env})
 
 
 if __name__ == '__main__':

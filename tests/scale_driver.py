@@ -1,8 +1,9 @@
 """Runs the operator-scaling kernel cases of one precision on the GPU, in a
 process of its own: `python tests/scale_driver.py <precision>` with precision
 f32 or f64 (default environment). Cases, references and bounds come from
-tests/spmm_cases_scale.py. Prints one JSON line per case. This is a plain
-module, not a test file.
+tests/spmm_cases_scale.py; the job loop, the refusal check and the guarded
+float64 vectors are tests/child_harness.py's. Prints one JSON line per case.
+This is a plain module, not a test file.
 
 Every float64 vector handed to the library sits between sentinels, checked
 after each call. Exact class: sums equal the host sums exactly (absolute 0
@@ -15,50 +16,28 @@ Real class (no split rows, so the launch is deterministic): the SpMM on the
 device-scaled handle equals, bit for bit, the SpMM on a second handle
 uploaded with the host-rounded values, and the sums are within the bound.
 """
-import json
-import os
 import sys
-import time
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from arrow_matrix_amd import hip  # noqa: E402
 from tests import spmm_cases as sc  # noqa: E402
 from tests import spmm_cases_scale as ss  # noqa: E402
+from tests.child_harness import Mismatch  # noqa: E402
+from tests.child_harness import f64_guards_intact as intact  # noqa: E402
 
-GUARD, PAD = -7.0, 16
+PAD = 16
 TORCH = {'f32': torch.float32, 'f64': torch.float64}
-
-
-class Mismatch(AssertionError):
-    pass
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def guarded(values):
     """(buffer, view): a float64 device vector between PAD sentinels."""
-    values = np.asarray(values, dtype=np.float64)
-    buf = torch.full((values.size + 2 * PAD,), GUARD, dtype=torch.float64,
-                     device='cuda')
-    view = buf[PAD:PAD + values.size]
-    view.copy_(torch.from_numpy(values))
-    return buf, view
-
-
-def intact(*bufs):
-    for buf in bufs:
-        h = buf.cpu().numpy()
-        if not ((h[:PAD] == GUARD).all() and (h[-PAD:] == GUARD).all()):
-            return False
-    return True
+    return ch.guarded_f64(values, PAD)
 
 
 def block(c, prec, vals=None):
@@ -75,7 +54,7 @@ def shapes(c):
 
 def sums_call(blk, views, absolute):
     blk.sums(*(v.data_ptr() if v is not None else 0 for v in views),
-             absolute=absolute, stream=_stream())
+             absolute=absolute, stream=ch.stream())
     torch.cuda.synchronize()
 
 
@@ -143,7 +122,8 @@ def spmm(blk, c, prec, feat, X0, X1, k):
     x0, x1 = _feat(prec, feat, X0), _feat(prec, feat, X1)
     C = torch.full((ss.out_rows(c), k), float('nan'), dtype=x0.dtype,
                    device='cuda')
-    blk.spmm_dual(x0.data_ptr(), x1.data_ptr(), C.data_ptr(), k, 0, _stream(),
+    blk.spmm_dual(x0.data_ptr(), x1.data_ptr(), C.data_ptr(), k, 0,
+                  ch.stream(),
                   feat_dtype='bfloat16' if feat == 'bf16' else None)
     torch.cuda.synchronize()
     return C
@@ -161,13 +141,13 @@ def check_scale(c, prec):
                             for f in fac))
         X0, X1 = ss.operands(c, 16)
         before = spmm(blk, c, prec, None, X0, X1, 16)
-        blk.scale(0, 0, 0, _stream())          # all NULL: nothing changes
+        blk.scale(0, 0, 0, ch.stream())          # all NULL: nothing changes
         torch.cuda.synchronize()
         again = spmm(blk, c, prec, None, X0, X1, 16)
         if not torch.equal(before.view(torch.uint8), again.view(torch.uint8)):
             raise Mismatch(f"{c['name']}: an all-NULL scale changed the result")
         blk.scale(*(v.data_ptr() if v is not None else 0 for v in views),
-                  stream=_stream())
+                  stream=ch.stream())
         torch.cuda.synchronize()
         if not intact(*(b for b in bufs if b is not None)):
             raise Mismatch(f"{c['name']} {tag}: sentinels overwritten by scale")
@@ -211,7 +191,7 @@ def check_empty(c, prec):
     blk = block(c, prec)
     bufs, views = zip(*(guarded(np.full(n, 3.0)) for n in shapes(c)))
     sums_call(blk, views, False)
-    blk.scale(*(v.data_ptr() for v in views), stream=_stream())
+    blk.scale(*(v.data_ptr() for v in views), stream=ch.stream())
     torch.cuda.synchronize()
     if not intact(*bufs) or not all((v.cpu().numpy() == 3.0).all()
                                     for v in views):
@@ -222,20 +202,18 @@ def check_empty(c, prec):
 def run_misuse(prec):
     lib = hip._load()
     blk = block(ss.CASES[0], prec)
-    rc = lib.arrow_csr_sums(blk._handle, None, None, None, 0, _stream())
-    msg = lib.arrow_last_error().decode()
-    if not (rc < 0 and 'all NULL' in msg):
-        raise Mismatch(f"sums with three NULL outputs: rc {rc}, {msg!r}")
+
+    def call(fn, *args):
+        return lambda: (fn(*args, ch.stream()),
+                        lib.arrow_last_error().decode())
+    ch.refused(call(lib.arrow_csr_sums, blk._handle, None, None, None, 0),
+               ('all NULL',), {})
     buf, view = guarded(np.full(8, 3.0))
-    for fn, args in ((lib.arrow_csr_sums, (view.data_ptr(),) * 3 + (0,)),
-                     (lib.arrow_csr_scale, (view.data_ptr(),) * 3)):
-        rc = fn(1 << 40, *args, _stream())
-        msg = lib.arrow_last_error().decode()
-        if not (rc < 0 and 'bad handle' in msg):
-            raise Mismatch(f"bad handle accepted: rc {rc}, {msg!r}")
-    torch.cuda.synchronize()
-    if not intact(buf) or not (view.cpu().numpy() == 3.0).all():
-        raise Mismatch("a refused call wrote")
+    ptrs = (view.data_ptr(),) * 3
+    for fn, args in ((lib.arrow_csr_sums, ptrs + (0,)),
+                     (lib.arrow_csr_scale, ptrs)):
+        ch.refused(call(fn, 1 << 40, *args), ('bad handle',),
+                   {'the vector': (buf, view, ch.F64_GUARD, np.full(8, 3.0))})
     return {}
 
 
@@ -257,23 +235,9 @@ def job_names(prec):
 
 def main(argv):
     prec = argv[1]
-    for var in sc.KERNEL_VARS:      # the default environment
-        assert os.environ.get(var) is None, var
-    assert torch.cuda.is_available(), "the scale driver needs a HIP GPU"
-    hip.set_device(torch.cuda.current_device())
-    for name, job in jobs(prec):
-        line = {'case': name, 'prec': prec}
-        t0 = time.perf_counter()
-        try:
-            line.update(job())
-            line['ok'] = True
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        line['ms'] = round(1e3 * (time.perf_counter() - t0), 1)
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+    ch.started_with(sc.KERNEL_VARS, {})     # the default environment
+    ch.open_gpu("the scale driver needs a HIP GPU")
+    return ch.run_jobs(jobs(prec), {'prec': prec})
 
 
 if __name__ == '__main__':

@@ -11,33 +11,28 @@ after every launch; one JSON line is printed per case and the process exits
 non-zero on the first mismatch.
 
 Everything is written once. What differs between the precisions is the data
-of a Precision record, as Prec<T> holds it for the kernels. This is a plain
-module, not a test file.
+of a Precision record, as Prec<T> holds it for the kernels; the job loop, the
+refusal check, the guarded buffers and the upload are tests/child_harness.py's,
+shared with every other driver. This is a plain module, not a test file.
 """
 import dataclasses
-import json
-import os
 import sys
-import time
 from typing import Any, Callable
 
 import numpy as np
 import torch
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if REPO not in sys.path:
-    sys.path.insert(0, REPO)
+if not __package__:         # started as a script: see tests/child_harness.py
+    import child_harness  # noqa: F401
+from tests import child_harness as ch  # noqa: E402
 
 from arrow_matrix_amd import hip  # noqa: E402
 from tests import spmm_cases as sc  # noqa: E402
 from tests import spmm_cases_bf16 as s16  # noqa: E402
 from tests import spmm_cases_f64 as s64  # noqa: E402
-
-PAD = 64                 # guard words before and after every view
-
-
-class Mismatch(AssertionError):
-    pass
+# the guarded buffers and Mismatch are the harness's, used through this module
+from tests.child_harness import (  # noqa: E402,F401
+    PAD, Mismatch, _words, fill_bits, guarded, guards_intact, host_bits)
 
 
 # ---------------------------------------------------------------------------
@@ -74,44 +69,6 @@ class Precision:
 
 
 # ---------------------------------------------------------------------------
-# guarded device buffers
-# ---------------------------------------------------------------------------
-
-def _words(prec, bits):
-    """The raw bits as a flat array of guard-buffer words."""
-    return np.ascontiguousarray(bits).view(prec.word).reshape(-1)
-
-
-def guarded(prec, bits, guard, device):
-    """A copy of the raw `bits` on `device` as a view into a larger buffer
-    of prec.word words, with PAD words holding `guard` on either side; the
-    view stays 16-byte aligned. Returns (buffer, view)."""
-    words = _words(prec, bits)
-    buf = torch.full((words.size + 2 * PAD,), guard,
-                     dtype=getattr(torch, prec.word), device=device)
-    view = buf[PAD:PAD + words.size]
-    view.copy_(torch.from_numpy(words))
-    assert view.data_ptr() % 16 == 0
-    return buf, view
-
-
-def guards_intact(buf, guard):
-    return bool((buf[:PAD] == guard).all().item()
-                and (buf[-PAD:] == guard).all().item())
-
-
-def host_bits(prec, view, shape):
-    """The view's words back on the host, as raw bits of `shape`."""
-    return view.cpu().numpy().view(prec.bits_dtype).reshape(shape)
-
-
-def fill_bits(prec):
-    """The raw bits of one element whose every word is c_fill."""
-    return np.full(prec.words_per_element, prec.c_fill,
-                   dtype=prec.word).view(prec.bits_dtype)[0]
-
-
-# ---------------------------------------------------------------------------
 # one case
 # ---------------------------------------------------------------------------
 
@@ -141,18 +98,9 @@ def launch(prec, case, m, X0v, X1v, C0_bits, remap):
     guards intact)."""
     k, beta = case['k'], case['beta']
     cbuf, cv = guarded(prec, C0_bits, prec.c_guard, 'cuda')
-    blk = hip.CsrBlockGPU(
-        arrays=((m['rows'], m['n0']), m['indptr'], m['cols'],
-                prec.a_values(case, m)),
-        row_ids=sc.row_ids(case), col_items=case.get('col_items', 0),
-        dtype=prec.struct_dtype)
-    prec.check_block(blk)
-    if case['queue'] is not None:
-        blk.set_queue(case['queue'])
-    if case.get('qblocks'):
-        blk.set_qblocks(case['qblocks'])
+    blk = ch.upload(prec, case, m)
     blk.set_xcd_remap(remap)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = ch.stream()
     outs = []
     for _ in range(2 if case.get('repeat') else 1):
         if not beta:
@@ -237,7 +185,7 @@ def run_spmm_case(prec, case):
 
 def run_route_case(prec, op, n, k):
     rc = prec.cases.route_case(op, n, k)
-    stream = torch.cuda.current_stream().cuda_stream
+    stream = ch.stream()
     _, src = guarded(prec, prec.bits(rc['src']), prec.x_guard, 'cuda')
     dbuf, dst = guarded(prec, prec.bits(rc['dst0']), prec.c_guard, 'cuda')
     idx = {key: torch.from_numpy(rc[key]).cuda()
@@ -273,38 +221,24 @@ def route_case_names(prec):
 # the two misuse jobs
 # ---------------------------------------------------------------------------
 
-def _refused(prec, fn, handle, dual, Xv, C0_bits, k, words):
-    """fn, through ctypes, for beta 0 and 1: a negative code, a message that
-    holds every one of `words`, and C keeps its bits (nothing is launched)."""
+def plain_call_refused(prec, fn, handle, dual, Xv, C0_bits, k, words):
+    """fn, a plain entry point through ctypes, is refused (ch.refused) for
+    beta 0 and 1, and C keeps its bits."""
     lib = hip._load()
-    stream = torch.cuda.current_stream().cuda_stream
+    xs = (Xv.data_ptr(),) * (2 if dual else 1)
     for beta in (0, 1):
         cbuf, cv = guarded(prec, C0_bits, prec.c_guard, 'cuda')
-        xs = (Xv.data_ptr(),) * (2 if dual else 1)
-        rc = fn(handle._handle, *xs, cv.data_ptr(), k, beta, stream)
-        msg = lib.arrow_last_error().decode()
-        torch.cuda.synchronize()
-        if not rc < 0:
-            raise Mismatch(f"misuse accepted (rc {rc}, k {k})")
-        if not all(w in msg for w in words):
-            raise Mismatch(f"message does not name {words}: {msg!r}")
-        if not (guards_intact(cbuf, prec.c_guard)
-                and (host_bits(prec, cv, C0_bits.shape) == C0_bits).all()):
-            raise Mismatch("C was written by a refused call")
-
-
-def _two_handles():
-    m = sc.matrix('std')
-    arrays = ((m['rows'], m['n0']), m['indptr'], m['cols'], m['vals'])
-    return m, hip.CsrBlockGPU(arrays=arrays), \
-        hip.CsrBlockGPU(arrays=arrays, dtype=np.float64)
+        ch.refused(lambda: (fn(handle._handle, *xs, cv.data_ptr(), k, beta,
+                               ch.stream()),
+                            lib.arrow_last_error().decode()),
+                   words, {'C': (cbuf, cv, prec.c_guard, C0_bits)})
 
 
 def run_handle_misuse(prec):
     """Each precision's handle passed to the other precision's SpMM entry
     point: refused, with a message naming both precisions."""
     lib = hip._load()
-    m, h32, h64 = _two_handles()
+    m, h64, h32 = ch.own_and_other(prec)         # a job of f64 alone
     if (lib.arrow_csr_dtype(h32._handle), lib.arrow_csr_dtype(h64._handle)) \
             != (32, 64):
         raise Mismatch("arrow_csr_dtype does not report 32 and 64")
@@ -317,7 +251,8 @@ def run_handle_misuse(prec):
                              (lib.arrow_spmm_dual_f64, True, h32),
                              (lib.arrow_spmm, False, h64),
                              (lib.arrow_spmm_dual, True, h64)):
-        _refused(prec, fn, handle, dual, Xv, C0, k, ('float32', 'float64'))
+        plain_call_refused(prec, fn, handle, dual, Xv, C0, k,
+                           ('float32', 'float64'))
     return dict(sentinels='intact')
 
 
@@ -325,7 +260,7 @@ def run_bf16_misuse(prec):
     """A float64 handle at arrow_spmm_bf16 / arrow_spmm_dual_bf16, and
     k = 12 on a float32 handle: refused, with a message naming the reason."""
     lib = hip._load()
-    m, h32, h64 = _two_handles()
+    m, h32, h64 = ch.own_and_other(prec)         # a job of bf16 alone
     rng = np.random.default_rng(16)
     for handle, k, words in ((h64, 8, ('float64', 'bfloat16')),
                              (h32, 12, ('k % 8', '12'))):
@@ -334,7 +269,7 @@ def run_bf16_misuse(prec):
         _, Xv = guarded(prec, X, prec.x_guard, 'cuda')
         for fn, dual in ((lib.arrow_spmm_bf16, False),
                          (lib.arrow_spmm_dual_bf16, True)):
-            _refused(prec, fn, handle, dual, Xv, C0, k, words)
+            plain_call_refused(prec, fn, handle, dual, Xv, C0, k, words)
     return dict(sentinels='intact')
 
 
@@ -465,35 +400,18 @@ PRECISIONS = {p.name: p for p in (
 def main(argv):
     prec, name = PRECISIONS[argv[1]], argv[2]
     variables, cases = prec.cases.env_table()[name]
-    for var in sc.KERNEL_VARS:      # started with exactly this entry's set
-        assert os.environ.get(var) == variables.get(var), var
+    ch.started_with(sc.KERNEL_VARS, variables)
+    ch.open_gpu("the SpMM driver needs a HIP GPU")
 
-    assert torch.cuda.is_available(), "the SpMM driver needs a HIP GPU"
-    hip.set_device(torch.cuda.current_device())
-
-    jobs = [(c['name'], c, lambda c=c: run_spmm_case(prec, c)) for c in cases]
+    jobs = [(c['name'], lambda c=c: run_spmm_case(prec, c), c) for c in cases]
     if name == 'default':
-        jobs += [(f'route_{op}_n{n}_k{k}', dict(op=op, n=n, k=k),
-                  lambda op=op, n=n, k=k: run_route_case(prec, op, n, k))
+        jobs += [(f'route_{op}_n{n}_k{k}',
+                  lambda op=op, n=n, k=k: run_route_case(prec, op, n, k),
+                  dict(op=op, n=n, k=k))
                  for op in sc.ROUTE_OPS for n, k in prec.route_shapes]
-        jobs += [(jname, {}, lambda fn=fn: fn(prec))
+        jobs += [(jname, lambda fn=fn: fn(prec))
                  for jname, fn in prec.extra_jobs]
-    for cname, spec, job in jobs:
-        line = {'case': cname, 'env': name}
-        line.update({key: spec[key] for key in
-                     ('matrix', 'kind', 'k', 'beta', 'queue', 'op', 'n')
-                     if key in spec})
-        t0 = time.perf_counter()
-        try:
-            line.update(job())
-            line['ok'] = True
-        except AssertionError as e:
-            line.update(ok=False, error=str(e)[:2000])
-        line['ms'] = round(1e3 * (time.perf_counter() - t0), 1)
-        print(json.dumps(line), flush=True)
-        if not line['ok']:
-            return 1
-    return 0
+    return ch.run_jobs(jobs, {'env': name})
 
 
 if __name__ == '__main__':

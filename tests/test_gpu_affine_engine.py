@@ -23,20 +23,12 @@ DRIVER = os.path.join(gpu_children.REPO, 'tests', 'engine_affine_driver.py')
 CHILD_LIMIT_S = 150      # process start + GPU initialisation + 3 x 3 tiny steps
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    gpu_children.fail_if_stopped()
-    for var in gpu_children.ENGINE_VARS:
-        assert var not in os.environ, var
-
-
 @pytest.mark.parametrize('precision', drv.PRECISIONS)
 @pytest.mark.parametrize('shape', ['L1', 'HUB'])
 def test_default_layout_is_fused_and_within_bound(shape, precision):
     """The single-launch layout carries the step in its write-back: within
     the bound and the tail kernel is never called. HUB has split rows."""
-    _need_gpu()
+    gpu_children.need_gpu()
     kwargs = getattr(drv, shape)
     arrow, tails, figures = drv.run(precision, **kwargs)
     eng0 = arrow.engines[0]
@@ -57,14 +49,11 @@ def test_default_layout_is_fused_and_within_bound(shape, precision):
 def test_environment_selected_layouts(mode):
     """Each layout in a child that starts with its environment; both folds
     are fused (no tail call), the others run the tail kernel once a step."""
-    _need_gpu()
+    gpu_children.need_gpu()
     variables, _, inside = drv.MODES[mode]
-    rc, lines, stderr = gpu_children.run_child(
-        [DRIVER, mode], variables, gpu_children.ENGINE_VARS, CHILD_LIMIT_S,
-        f"affine engine child '{mode}'")
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, f"{mode}: {bad[0]}\n{stderr}"
-    assert rc == 0, stderr
+    lines = gpu_children.child_ok(
+        (DRIVER, mode), [DRIVER, mode], variables, gpu_children.ENGINE_VARS,
+        CHILD_LIMIT_S, f"affine engine child '{mode}'", drv.PRECISIONS)
     assert set(lines) == set(drv.PRECISIONS)
     for ln in lines.values():
         assert ln['tails'] == (0 if inside else 3)
@@ -76,7 +65,7 @@ def test_captured_step_equals_the_uncaptured_step(shape, precision):
     """set_affine_step allocates; step() does not: after one warm-up step a
     step captured under torch.cuda.graph replays to the bits of the same
     step run directly."""
-    _need_gpu()
+    gpu_children.need_gpu()
     arrow, A, perm0, X, R = drv.build(precision=precision,
                                       **getattr(drv, shape))
     arrow.B.set_features(X[perm0].copy())
@@ -99,7 +88,7 @@ def test_captured_step_equals_the_uncaptured_step(shape, precision):
 
 @pytest.mark.parametrize('precision', drv.PRECISIONS)
 def test_clear_affine_step_restores_the_plain_step(precision):
-    _need_gpu()
+    gpu_children.need_gpu()
     a, A, perm0, X, R = drv.build(precision=precision, **drv.L1)
     b, *_ = drv.build(precision=precision, **drv.L1)
     a.B.set_features(X[perm0].copy())
@@ -118,7 +107,7 @@ def test_clear_affine_step_restores_the_plain_step(precision):
 
 
 def test_refusals_on_the_gpu_engine():
-    _need_gpu()
+    gpu_children.need_gpu()
     from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
     e = ArrowSlimMPI(None, tiles_per_side=2, device='gpu')
     e.zero_rhs(8, 8)
@@ -139,7 +128,7 @@ def test_refusals_on_the_gpu_engine():
 
 
 def test_bench_spmm_gpu_damping():
-    _need_gpu()
+    gpu_children.need_gpu()
     from arrow_matrix_amd.arrow_bench import bench_spmm
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as td:

@@ -25,15 +25,6 @@ DRIVER = os.path.join(REPO, 'tests', 'engine_bf16_driver.py')
 CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
 
 
-def _need_gpu():
-    """Every test starts here: after a child of any test module has
-    aborted, faulted or hit its limit, no later test starts GPU work,
-    in-process or not."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    gpu_children.fail_if_stopped()
-
-
 def _within(results, goldens, bounds):
     assert len(results) == 3
     for step, (C, G, B) in enumerate(zip(results, goldens, bounds)):
@@ -56,7 +47,7 @@ def _within(results, goldens, bounds):
     ([5], 512, 8, 5, dict(hub_rows=2, hub_deg=8000)),
 ])
 def test_engine_gpu_bf16_steps_within_bound(n_blocks, width, k, seed, extra):
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     for var in gpu_children.ENGINE_VARS:
         assert var not in os.environ, var
     if extra.get('hub_rows'):
@@ -74,7 +65,7 @@ def test_engine_gpu_bf16_steps_within_bound(n_blocks, width, k, seed, extra):
 @pytest.mark.parametrize('mode', list(drv.MODES))
 def test_engine_gpu_bf16_paths(mode):
     """Each environment-selected path, in a child that starts with it."""
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     variables, kwargs = drv.MODES[mode]
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, 'out.npy')
@@ -90,7 +81,7 @@ def test_engine_gpu_bf16_paths(mode):
 def test_float32_engine_still_meets_its_gate_in_the_same_session():
     """The float32 engine on the matrix of the first bf16 case, after bf16
     launches ran in this process: the gate of test_gpu_engine.py."""
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     results, goldens, _, arrow = drv.run_engine(
         n_blocks=[3], width=64, k=32, seed=0, dtype=np.float32, iters=1)
     assert arrow.B.result_tile().dtype == torch.float32
@@ -98,7 +89,7 @@ def test_float32_engine_still_meets_its_gate_in_the_same_session():
 
 
 def test_zero_rhs_refuses_bad_width_and_other_dtypes():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
     from arrow_matrix_amd.arrow_mpi import ArrowMPI
     e = ArrowSlimMPI(None, tiles_per_side=2, device='gpu',
@@ -121,7 +112,7 @@ def test_zero_rhs_refuses_bad_width_and_other_dtypes():
 
 
 def test_set_features_rounds_numpy_once_and_takes_tensors():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
     from arrow_matrix_amd.backends import make_backend
     be = make_backend('gpu', torch.bfloat16)
@@ -145,7 +136,7 @@ def test_set_features_rounds_numpy_once_and_takes_tensors():
 
 
 def test_bench_spmm_gpu_bf16():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.arrow_bench import bench_spmm
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as td:

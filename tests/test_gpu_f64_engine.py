@@ -28,15 +28,6 @@ TOL = 1e-12
 CHILD_LIMIT_S = 90       # process start + GPU initialisation + 3 tiny steps
 
 
-def _need_gpu():
-    """Every test starts here: after a child of any test module has
-    aborted, faulted or hit its limit, no later test starts GPU work,
-    in-process or not."""
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    gpu_children.fail_if_stopped()
-
-
 def _close(C, G):
     scale = float(np.abs(G).max())
     np.testing.assert_allclose(C, G, rtol=TOL, atol=TOL * scale)
@@ -54,7 +45,7 @@ def _close(C, G):
     ([5], 512, 8, 5, dict(hub_rows=2, hub_deg=8000)),
 ])
 def test_engine_gpu_f64_matches_golden(n_blocks, width, k, seed, extra):
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     if extra.get('hub_rows'):
         B0 = drv.make_decomposition(n_blocks, width, seed, **extra)[0][0]
         assert np.diff(B0.indptr).max() > SEG_NNZ
@@ -65,7 +56,7 @@ def test_engine_gpu_f64_matches_golden(n_blocks, width, k, seed, extra):
 
 
 def test_engine_gpu_f64_iterated():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     results, goldens, _ = drv.run_f64([3, 2], 64, 16, 7, iters=3)
     assert len(results) == 3
     for C, G in zip(results, goldens):
@@ -87,7 +78,7 @@ def _default_results(kwargs):
 @pytest.mark.parametrize('mode', list(drv.MODES))
 def test_engine_gpu_f64_paths(mode):
     """Each environment-selected path, in a child that starts with it."""
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     variables, kwargs = drv.MODES[mode]
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, 'out.npy')
@@ -105,7 +96,7 @@ def test_engine_gpu_f64_paths(mode):
 
 
 def test_zero_rhs_dtype_is_fixed_at_construction():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.arrow_slim import ArrowSlimMPI
     from arrow_matrix_amd.arrow_mpi import ArrowMPI
     e64 = ArrowSlimMPI(None, tiles_per_side=2, device='gpu', dtype=np.float64)
@@ -124,7 +115,7 @@ def test_zero_rhs_dtype_is_fixed_at_construction():
 
 
 def test_make_backend_gpu_f64_and_other_dtypes():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.backends import make_backend
     be = make_backend('gpu', np.float64)
     assert be.np_dtype == np.float64 and be.torch_dtype == torch.float64
@@ -135,7 +126,7 @@ def test_make_backend_gpu_f64_and_other_dtypes():
 
 
 def test_petsc_gpu_f64():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from scipy import sparse
     from arrow_matrix_amd.matrix_slice import MatrixSlice
     from arrow_matrix_amd.spmm_petsc import SpmmPETSc
@@ -152,7 +143,7 @@ def test_petsc_gpu_f64():
 
 
 def test_bench_spmm_gpu_f64():
-    _need_gpu()
+    gpu_children.need_gpu(clean=())
     from arrow_matrix_amd.arrow_bench import bench_spmm
     cwd = os.getcwd()
     with tempfile.TemporaryDirectory() as td:

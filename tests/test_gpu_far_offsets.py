@@ -34,28 +34,15 @@ DRIVER = os.path.join(gpu_children.REPO, 'tests', 'far_driver.py')
 LIMIT_S = {'f32': 50, 'f64': 80, 'bf16': 20}
 ALLOWANCE = 1 << 30
 
-_results = {}
-
-
-def _child(prec):
-    if prec not in _results:
-        _results[prec] = gpu_children.run_child(
-            [DRIVER, prec], {}, KERNEL_VARS, LIMIT_S[prec],
-            f"{prec} far-offset child")
-    return _results[prec]
-
 
 @pytest.mark.parametrize('prec', far.PRECISIONS)
 def test_far_offsets(prec):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    rc, lines, stderr = _child(prec)
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, f"{prec}: {bad[0]}"
-    assert rc == 0, f"{prec}: driver exit status {rc}\n{stderr}"
     peaks = far.job_peaks(prec)
-    missing = [c for c in peaks if c not in lines]
-    assert not missing, f"{prec}: cases not run: {missing[:5]}"
+    lines = gpu_children.child_ok(
+        (DRIVER, prec), [DRIVER, prec], {}, KERNEL_VARS, LIMIT_S[prec],
+        f"{prec} far-offset child", peaks)
     over = {c: (lines[c]['peak_bytes'], peaks[c]) for c in peaks
             if lines[c]['peak_bytes'] > peaks[c] + ALLOWANCE}
     assert not over, f"{prec}: peak memory above the derived figure: {over}"

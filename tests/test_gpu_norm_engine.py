@@ -19,20 +19,12 @@ DRIVER = os.path.join(gpu_children.REPO, 'tests', 'engine_norm_driver.py')
 CHILD_LIMIT_S = 150      # process start + GPU initialisation + 6 x 2 tiny steps
 
 
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    gpu_children.fail_if_stopped()
-    for var in gpu_children.ENGINE_VARS:
-        assert var not in os.environ, var
-
-
 @pytest.mark.parametrize('affine', [False, True])
 @pytest.mark.parametrize('precision', drv.PRECISIONS)
 def test_default_layout_measures_in_its_launch(precision, affine):
     """The norm entry point is the one called, with or without an affine
     step, and the stand-alone pass never runs."""
-    _need_gpu()
+    gpu_children.need_gpu()
     _, _, fused = drv.MODES['default']
     arrow, n_fused, n_alone, _ = drv.run_tracked(precision, affine, **drv.ead.L1)
     assert arrow.engines[0]._A_all is not None
@@ -41,14 +33,12 @@ def test_default_layout_measures_in_its_launch(precision, affine):
 
 @pytest.mark.parametrize('mode', [m for m in drv.MODES if m != 'default'])
 def test_environment_selected_layouts(mode):
-    _need_gpu()
+    gpu_children.need_gpu()
     variables, _, _ = drv.MODES[mode]
-    rc, lines, stderr = gpu_children.run_child(
-        [DRIVER, mode], variables, gpu_children.ENGINE_VARS, CHILD_LIMIT_S,
-        f"norm engine child '{mode}'")
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, f"{mode}: {bad[0]}\n{stderr}"
-    assert rc == 0, stderr
+    lines = gpu_children.child_ok(
+        (DRIVER, mode), [DRIVER, mode], variables, gpu_children.ENGINE_VARS,
+        CHILD_LIMIT_S, f"norm engine child '{mode}'",
+        [f'{p}_affine{a}' for p in drv.PRECISIONS for a in (0, 1)])
     assert set(lines) == {f'{p}_affine{a}' for p in drv.PRECISIONS
                           for a in (0, 1)}
     for ln in lines.values():
@@ -60,7 +50,7 @@ def test_iterate_stops_on_a_contraction(precision):
     """Row-scaled matrix at damping 0.5: iterate stops before max_steps with
     rel <= tol, after as many steps as the cpu engine takes (which has no
     bfloat16)."""
-    _need_gpu()
+    gpu_children.need_gpu()
     steps, rel = drv.run_iterate(precision, 'gpu')
     assert 1 < steps < drv.ITER_MAX
     assert rel <= drv.ITER_TOL[precision]
@@ -71,7 +61,7 @@ def test_iterate_stops_on_a_contraction(precision):
 
 
 def test_untracked_engine_refuses_to_report():
-    _need_gpu()
+    gpu_children.need_gpu()
     arrow, *_ = drv.ead.build(precision='float32', **drv.ead.L1)
     with pytest.raises(RuntimeError, match='track_step_norms'):
         arrow.last_step_norms()

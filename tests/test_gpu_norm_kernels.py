@@ -22,28 +22,16 @@ DRIVER = os.path.join(gpu_children.REPO, 'tests', 'norm_driver.py')
 # `zero_rows` on the host, the stand-alone shapes and the misuse calls
 LIMIT_S = {'default': 240}
 
-_results = {}
-
-
-def _child(prec, env):
-    if (prec, env) not in _results:
-        _results[prec, env] = gpu_children.run_child(
-            [DRIVER, prec, env], sn.ENVS[env], KERNEL_VARS,
-            LIMIT_S.get(env, 120), f"{prec} norm kernel child '{env}'")
-    return _results[prec, env]
-
 
 @pytest.mark.parametrize('env', list(sn.ENVS))
 @pytest.mark.parametrize('prec', sn.PRECISIONS)
 def test_norm_kernels(prec, env):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
-    rc, lines, stderr = _child(prec, env)
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, f"{prec}/{env}: {bad[0]}"
-    assert rc == 0, f"{prec}/{env}: driver exit status {rc}\n{stderr}"
-    missing = [c for c in drv.job_names(prec, env) if c not in lines]
-    assert not missing, f"{prec}/{env}: cases not run: {missing[:5]}"
+    lines = gpu_children.child_ok(
+        (DRIVER, prec, env), [DRIVER, prec, env], sn.ENVS[env], KERNEL_VARS,
+        LIMIT_S.get(env, 120), f"{prec} norm kernel child '{env}'",
+        drv.job_names(prec, env))
     # every scheduler the environment can select was launched
     scheds = {ln['scheduler'] for ln in lines.values() if 'scheduler' in ln}
     want = {'default': {sn.GRID, sn.QBLOCK, sn.QWAVE},

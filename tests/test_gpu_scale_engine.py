@@ -6,7 +6,7 @@ import os
 import pytest
 
 from tests import engine_scale_driver as esd
-from tests.gpu_children import ENGINE_VARS, REPO, run_child
+from tests.gpu_children import ENGINE_VARS, REPO, child_ok
 
 pytestmark = pytest.mark.gpu
 DRIVER = os.path.join(REPO, 'tests', 'engine_scale_driver.py')
@@ -14,10 +14,7 @@ DRIVER = os.path.join(REPO, 'tests', 'engine_scale_driver.py')
 
 @pytest.mark.parametrize('mode', sorted(esd.MODES))
 def test_scale_engine(mode):
-    rc, lines, stderr = run_child([DRIVER, mode, 'gpu'], esd.MODES[mode][0],
-                                  ENGINE_VARS, 300,
-                                  f"scale engine child '{mode}'")
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, bad[0]
-    assert rc == 0, f"driver exit status {rc}\n{stderr}"
+    lines = child_ok((DRIVER, mode), [DRIVER, mode, 'gpu'], esd.MODES[mode][0],
+                     ENGINE_VARS, 300, f"scale engine child '{mode}'",
+                     esd.PRECISIONS['gpu'])
     assert sorted(lines) == sorted(esd.PRECISIONS['gpu'])

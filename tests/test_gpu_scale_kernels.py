@@ -5,7 +5,7 @@ import os
 import pytest
 
 from tests import scale_driver
-from tests.gpu_children import REPO, run_child
+from tests.gpu_children import REPO, child_ok
 from tests.spmm_cases import KERNEL_VARS
 
 pytestmark = pytest.mark.gpu
@@ -14,10 +14,5 @@ DRIVER = os.path.join(REPO, 'tests', 'scale_driver.py')
 
 @pytest.mark.parametrize('prec', ['f32', 'f64'])
 def test_scale_kernels(prec):
-    rc, lines, stderr = run_child([DRIVER, prec], {}, KERNEL_VARS, 300,
-                                  f"{prec} scale kernel child")
-    bad = [ln for ln in lines.values() if not ln['ok']]
-    assert not bad, bad[0]
-    assert rc == 0, f"driver exit status {rc}\n{stderr}"
-    missing = [c for c in scale_driver.job_names(prec) if c not in lines]
-    assert not missing, f"cases not run: {missing}"
+    child_ok((DRIVER, prec), [DRIVER, prec], {}, KERNEL_VARS, 300,
+             f"{prec} scale kernel child", scale_driver.job_names(prec))
