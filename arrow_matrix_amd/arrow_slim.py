@@ -632,10 +632,24 @@ class ArrowSlimMPI(ArrowMatrix):
         self._affine = None
         self._R = None
 
-    def _affine_tail(self, affine: AffineStep) -> None:
+    def _split_col_carries(self, affine: Optional[AffineStep]) -> bool:
+        """True when the launches of the split-col layout (ARROW_SPLIT_COL=1,
+        single process) carry the affine step for every row below block row
+        0. Its rows are written twice, by the rest launch and by the
+        hub-sorted beta=1 launch; a tail over them would be a third pass and,
+        for bf16 features, a third rounding. The one place that decides it."""
+        return (affine is not None and self.backend.device == 'cuda'
+                and self._A_col is not None and bool(self._A_rest)
+                and self.comm.size == 1 and self.first_block == 0
+                and self._A_bd_lo is None and self._A_bd_hi is None)
+
+    def _affine_tail(self, affine: AffineStep, rows: Optional[int] = None) -> None:
         """C = alpha * C + gamma * R on this rank's finished result: the
-        layouts whose result no single launch finishes."""
-        self.backend.axpby_rows(self.C_i, affine.R, affine.alpha, affine.gamma)
+        layouts whose result no single launch finishes. rows: the leading
+        rows only (split-col: block row 0)."""
+        C = self.C_i if rows is None else self.C_i[:rows]
+        R = affine.R if rows is None or affine.R is None else affine.R[:rows]
+        self.backend.axpby_rows(C, R, affine.alpha, affine.gamma)
         # a cached X_0 (the allreduce_x0 fast path) holds the plain C_0
         self._x0_valid = False
 
@@ -914,7 +928,9 @@ class ArrowSlimMPI(ArrowMatrix):
             self._prev_result = self.C_i
         if not self._launch_finishes_step:
             if affine is not None:
-                self._affine_tail(affine)
+                # split-col: the rest rows were finished by their launches
+                self._affine_tail(affine, rows=w if self._split_col_carries(
+                    affine) else None)
             if norm_acc is not None:
                 self._measure_result(norm_acc)
 
@@ -1038,17 +1054,26 @@ class ArrowSlimMPI(ArrowMatrix):
             self._pending_x0_works = []
         if bcast_work is not None:
             bcast_work.wait()  # rest reads X_0
+        # split-col with an affine step (_split_col_carries): the rest
+        # launches carry alpha and gamma * R of their rows, the hub-sorted
+        # beta=1 launch alpha only, as the folded launches do; the tail then
+        # runs on block row 0 alone (_spmm_step)
+        step = affine if self._split_col_carries(affine) else AffineStep()
         if self._A_rest:
             for h, lo, hi in self._A_rest:
-                C_sub = self.C_i[self._rest_row_offset + lo:
-                                 self._rest_row_offset + hi]
-                self._timed(lambda h=h, C_sub=C_sub:
-                            be.spmm_dual(h, self.X_i, self.X_0, C_sub, 0),
+                r_lo, r_hi = (self._rest_row_offset + lo,
+                              self._rest_row_offset + hi)
+                C_sub = self.C_i[r_lo:r_hi]
+                R_sub = None if step.R is None else step.R[r_lo:r_hi]
+                self._timed(lambda h=h, C_sub=C_sub, R_sub=R_sub:
+                            be.spmm_dual(h, self.X_i, self.X_0, C_sub, 0,
+                                         step.alpha, step.gamma, R_sub),
                             h.nnz, C_sub.shape[0], h.x_rows)
         if self._A_col is not None:
             h = self._A_col
             C_full = self.C_i[self._rest_row_offset:self.n_owned * w]
-            self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_0, C_full, 1),
+            self._timed(lambda: be.spmm_dual(h, self.X_i, self.X_0, C_full, 1,
+                                             step.alpha),
                         h.nnz, h.shape[0], h.x_rows)
 
         # banded boundary off-diagonals against the received halo tiles

@@ -59,6 +59,33 @@ def test_environment_selected_layouts(mode):
         assert ln['tails'] == (0 if inside else 3)
 
 
+@pytest.mark.parametrize('precision', drv.PRECISIONS)
+def test_split_col_launches_carry_the_step(monkeypatch, precision):
+    """ARROW_SPLIT_COL=1 writes a row below block row 0 twice (rest launch,
+    hub-sorted beta = 1 launch): those launches carry the step, and the tail
+    runs on block row 0 alone, so no element is stored more than twice (the
+    bound counts two roundings of bf16 features). The layout variables are
+    read when the structures are built, so this runs in-process,
+    grid-stride."""
+    gpu_children.need_gpu()
+    from arrow_matrix_amd.backends import GpuBackend
+    monkeypatch.setenv('ARROW_FUSE_ALL', '0')
+    monkeypatch.setenv('ARROW_SPLIT_COL', '1')
+    tail_rows = []
+    inner = GpuBackend.axpby_rows
+
+    def recorded(self, C, *args, **kwargs):
+        tail_rows.append(C.shape[0])
+        return inner(self, C, *args, **kwargs)
+    monkeypatch.setattr(GpuBackend, 'axpby_rows', recorded)
+    shape = dict(drv.L1, hub_rows=2)
+    arrow, tails, figures = drv.run(precision, **shape)
+    eng0 = arrow.engines[0]
+    assert eng0._A_all is None and eng0._A_col is not None and eng0._A_rest
+    assert len(figures) == 3
+    assert tails == 3 and tail_rows == [shape['width']] * 3
+
+
 @pytest.mark.parametrize('shape,precision', [('L1', 'float32'),
                                              ('HUB', 'bfloat16')])
 def test_captured_step_equals_the_uncaptured_step(shape, precision):
