@@ -1080,8 +1080,11 @@ class ArrowSlimMPI(ArrowMatrix):
         for bd, halo in ((self._A_bd_lo, self.X_halo_lo),
                          (self._A_bd_hi, self.X_halo_hi)):
             if bd is not None:
+                # `local` counts rows of the rest structure, which starts
+                # below block row 0 on the rank that owns it
                 hdl, local = bd
-                Cr = self.C_i[local:local + w]
+                row = self._rest_row_offset + local
+                Cr = self.C_i[row:row + w]
                 self._timed(lambda: be.spmm_block(hdl, halo, Cr, 1),
                             hdl.nnz, w, w)
         if par:
